@@ -688,15 +688,15 @@ int ikgpu_dls_solve_batch(const ikgpu_problem *p, int64_t B, const double *q0, c
                 });
             const bool on_static = p->gen.generic_build == 2 || p->visitor_static;
             const uint64_t key = p->gen.generic_build == 2 ? p->gen.generic_key : p->visitor_static_key;
-            const hipError_t ev = on_static ? ikgpu::rtc_launch_generic_static(p->gen, key, io, *params, st, &p->dev.queues)
+            const hipError_t ev = on_static ? ikgpu::rtc_launch_generic_static(p->gen, key, io, *params, st, p->dev.queues)
                                             : ikgpu::launch_dls_generic(p->gen, p->dev, io, *params, st, /*force_lane=*/true);
             if (ev != hipSuccess) return hip_fail(ev, "launching the generic DLS kernel (derived visitor)");
             return static_cast<int>(IKGPU_OK);
         }
-        hipError_t e = p->dls_on_static_gen                      ? ikgpu::rtc_launch_generic_static(p->gen, p->gen.generic_key, io, *params, st, &p->dev.queues)
+        hipError_t e = p->dls_on_static_gen                      ? ikgpu::rtc_launch_generic_static(p->gen, p->gen.generic_key, io, *params, st, p->dev.queues)
                        : p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_dls_chain(p->host, p->dev, io, *params, st)
                        : p->host.kind == ikgpu::KernelKind::Tree ? ikgpu::launch_dls_tree(p->host, p->dev, io, *params, st)
-                       : p->host.generic_build == 2              ? ikgpu::rtc_launch_generic_static(p->host, p->host.generic_key, io, *params, st, &p->dev.queues)
+                       : p->host.generic_build == 2              ? ikgpu::rtc_launch_generic_static(p->host, p->host.generic_key, io, *params, st, p->dev.queues)
                                                                  : ikgpu::launch_dls_generic(p->host, p->dev, io, *params, st);
         if (e != hipSuccess) return hip_fail(e, "launching the DLS kernel");
         return static_cast<int>(IKGPU_OK);

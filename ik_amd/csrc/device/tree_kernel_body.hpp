@@ -224,7 +224,43 @@ __device__ __forceinline__ void dls_tree_refill_body(const TreeKernelArgs<NJ, NC
         }
     }
 }
+
+// While chain 1 is evaluated, chain 0's factor (L packed, W, u: 77 doubles for NJ = 7) is parked in LDS as [entry][lane]: consecutive
+// lanes hit consecutive 8-byte words, so every ds_write_b64 / ds_read_b64 is conflict-free (the tree kernels' `park`).
+template <int NJ>
+struct LdsPark {
+    static constexpr int kL = NJ * (NJ + 1) / 2;
+    static constexpr int kEntries = kL + NJ * 6 + NJ;
+    double (*buf)[64];
+    int lane;
+    __device__ __forceinline__ void store(const LegFactor<NJ> &F) const {
+#pragma unroll
+        for (int e = 0; e < kL; ++e) buf[e][lane] = F.L[e];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) buf[kL + j * 6 + c][lane] = F.W[j][c];
+            buf[kL + NJ * 6 + j][lane] = F.u[j];
+        }
+    }
+    __device__ __forceinline__ void load(LegFactor<NJ> &F) const {
+#pragma unroll
+        for (int e = 0; e < kL; ++e) F.L[e] = buf[e][lane];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) F.W[j][c] = buf[kL + j * 6 + c][lane];
+            F.u[j] = buf[kL + NJ * 6 + j][lane];
+        }
+    }
+};
 #endif  // IKD_HIP_LANG
+
+// Placement masks with a dedicated instantiation of the chain and tree kernels: the Cassie leg chains (knee, shin, tarsus, foot and
+// the foot frame are pure translations: 0xf8) and the UR5 arm (0x05).  Any other model runs the SMASK = 0 build.
+template <int NJ> struct HotMask { static constexpr int value = 0; };
+template <> struct HotMask<7> { static constexpr int value = 0xf8; };
+template <> struct HotMask<6> { static constexpr int value = 0x05; };
 
 // Stage kernel: world placement of every task frame and the stacked weighted error / dense Jacobian
 // (reference ik/ik/data.cpp:25-58).  Rows are emitted in task order with each task's kinematic type

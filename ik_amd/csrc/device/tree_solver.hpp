@@ -361,7 +361,7 @@ IKD_FN void se3_compose_struct(double (&R)[9], double (&p)[3], ConstPtr c, int i
 // kernel's code for the same leg, kernels_hot.hip); the launcher takes the hot build only for chains that carry it.
 constexpr uint64_t kTreeHotCode7[3] = {0x04f0208cce8c7664ull, 0x395959cacad65656ull, 0x000001cacace5656ull};
 template <int NJ> struct TreeHotStruct { typedef void type; static constexpr int mask = 0; };
-template <> struct TreeHotStruct<7> { typedef ChainStruct<kTreeHotCode7[0], kTreeHotCode7[1], kTreeHotCode7[2]> type; static constexpr int mask = 0xf8; };   // (mask: the code's identity-rotation placements, kernels.hip HotMask)
+template <> struct TreeHotStruct<7> { typedef ChainStruct<kTreeHotCode7[0], kTreeHotCode7[1], kTreeHotCode7[2]> type; static constexpr int mask = 0xf8; };   // (mask: the code's identity-rotation placements, tree_kernel_body.hpp HotMask)
 
 // Posture rows on the joints of one chain (wave-uniform description; targets per lane).
 struct ChainPosture {

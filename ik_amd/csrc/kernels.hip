@@ -27,6 +27,7 @@ constexpr int kBlock = 64;  // one wave64 per workgroup: 1024 workgroups at B = 
 
 using ikdev::ChainDesc;
 using ikdev::ChainKernelArgs;
+using ikdev::HotMask;
 
 // Stage the chain table HBM -> LDS with coalesced loads; every lane then reads it by broadcast.
 template <int NJ>
@@ -87,12 +88,6 @@ __global__ __launch_bounds__(256) void chain_pass_through_kernel(const PassThrou
     }
 }
 
-// Placement masks with a dedicated instantiation: the Cassie leg chains (knee, shin, tarsus, foot and the foot frame
-// are pure translations: 0xf8) and the UR5 arm (0x05).  Any other model runs the SMASK = 0 build.
-template <int NJ> struct HotMask { static constexpr int value = 0; };
-template <> struct HotMask<7> { static constexpr int value = 0xf8; };
-template <> struct HotMask<6> { static constexpr int value = 0x05; };
-
 template <int NJ, int KT>
 __global__ __launch_bounds__(kBlock) void eval_chain_kernel(const ChainKernelArgs<NJ> a) {
     __shared__ double lds_desc[sizeof(ChainDesc<NJ>) / sizeof(double)];
@@ -110,86 +105,44 @@ __global__ __launch_bounds__(kBlock) void fk_chain_kernel(const ChainKernelArgs<
 template <int NJ>
 ChainKernelArgs<NJ> make_args(const ProblemHost &ph, const DeviceTables &dt) {
     ChainKernelArgs<NJ> a{};
-    fill_chain_args(ph, a.ref_pl, a.qidx, a.vidx, &a.nq, &a.nv, &a.prm.priority, &a.prm.idmask, &a.prm.unit_weights);
-    a.desc = reinterpret_cast<const ChainDesc<NJ> *>(dt.chain_desc);
-    a.lower = dt.lower;
-    a.upper = dt.upper;
-    a.q_in_chain = dt.q_in_chain;
+    fill_chain_kernel_args(a, ph, dt);
     return a;
 }
 
 inline dim3 grid_for(int64_t B) { return dim3(static_cast<unsigned>((B + kBlock - 1) / kBlock)); }
 
-// A lane-refill launch: the launch's queue slot, an iteration-count array when the caller passed none (the pass-through kernel
-// reads it), the refill kernel, then the entries of q outside the chain.
-template <int NJ, class LaunchFn>
-hipError_t run_refill(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, ChainKernelArgs<NJ> &a, hipStream_t stream, LaunchFn launch) {
-    hipError_t e = hipSuccess;
-    unsigned long long *queue = dt.queues.slot_for(stream, &e);
-    if (!queue) return e;
-    int32_t *iters = io.iters;
-    void *tmp = nullptr;
-    if (!iters) {
-        if ((e = hipMallocAsync(&tmp, sizeof(int32_t) * static_cast<size_t>(io.B), stream)) != hipSuccess) return e;
-        iters = static_cast<int32_t *>(tmp);
-    }
-    launch(queue, iters);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_chain_pass_through(ph, dt, io, iters, stream);
-    if (tmp) {
-        const hipError_t f = hipFreeAsync(tmp, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
+// One build of the chain kernel (SM: its compile-time placement mask and weights) in the stop-rule mode the batch asks for.
+template <int NJ, int KT, int SM>
+hipError_t run_dls_build(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream,
+                         ChainKernelArgs<NJ> &a) {
+    const int64_t rgrid = refill_grid(reinterpret_cast<const void *>(dls_chain_refill_kernel<NJ, KT, SM>), io.B);
+    return run_stop_rule(dt.queues, io, prm, stream, a, false, rgrid, PassThrough{&ph, &dt}, [&] {
+        hipLaunchKernelGGL((dls_chain_kernel<NJ, KT, SM>), grid_for(io.B), dim3(kBlock), 0, stream, a);
+        return hipGetLastError();
+    }, [&](unsigned long long *queue, int chunk) {
+        hipLaunchKernelGGL((dls_chain_refill_kernel<NJ, KT, SM>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, queue, chunk);
+        return hipGetLastError();
+    });
 }
 
 template <int NJ, int KT>
 hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm,
                    hipStream_t stream) {
     ChainKernelArgs<NJ> a = make_args<NJ>(ph, dt);
-    a.prm.max_iterations = prm.max_iterations;
-    a.prm.lam2 = prm.damping * prm.damping;
-    a.prm.step_length = prm.step_length;
-    a.prm.stop_sq_tol = prm.stop_sq_tol;
-    a.layout = io.layout;
-    a.B = io.B;
-    a.q0 = io.q0;
-    a.targets = io.targets;
-    a.q_out = io.q_out;
-    a.success = io.success;
-    a.iters = io.iters;
+    fill_solve_args(a, io, prm);
     // two builds per shape: the hot one (known placement mask + unit weights, all folded at compile time) and the
     // general one (nothing skipped, weights always applied); neither has a branch inside the iteration
     // ... and, for the shapes with a known mask, one in between: the mask folded, the weights applied (a weighted task on a
     // Cassie leg or a UR arm keeps the skipped placement products)
     constexpr int kMask = HotMask<NJ>::value;
     constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
-    // stop-rule mode on a batch larger than the machine: lane refill (same lane program, persistent waves), then the entries outside the chain
-#define IKGPU_CHAIN_LAUNCH(SM)                                                                                                  \
-    do {                                                                                                                        \
-        const void *rk = reinterpret_cast<const void *>(dls_chain_refill_kernel<NJ, KT, SM>);                                    \
-        const int64_t rgrid = refill_grid(rk, io.B);                                                                            \
-        const int mode = stop_rule_mode(prm, io.B, rgrid, stream, false);                                                             \
-        if (mode == kStopRefill) return run_refill<NJ>(ph, dt, io, a, stream, [&](unsigned long long *queue, int32_t *it) {      \
-            a.iters = it;                                                                                                       \
-            hipLaunchKernelGGL((dls_chain_refill_kernel<NJ, KT, SM>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, queue, refill_chunk(io.B, rgrid)); \
-        });                                                                                                                     \
-        if (mode == kStopTwoPhase) return run_two_phase(dt.queues, io, stream, a, false, [&] {                                               \
-            hipLaunchKernelGGL((dls_chain_kernel<NJ, KT, SM>), grid_for(io.B), dim3(kBlock), 0, stream, a);                      \
-        }, [&](unsigned long long *queue) {                                                                                     \
-            hipLaunchKernelGGL((dls_chain_refill_kernel<NJ, KT, SM>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, queue, refill_chunk(io.B, rgrid)); \
-        });                                                                                                                     \
-        hipLaunchKernelGGL((dls_chain_kernel<NJ, KT, SM>), grid_for(io.B), dim3(kBlock), 0, stream, a);                          \
-        return hipGetLastError();                                                                                               \
-    } while (0)
     if constexpr (kMask != 0) {
         if ((a.prm.idmask & kMask) == kMask) {
-            if (a.prm.unit_weights) IKGPU_CHAIN_LAUNCH(kHot);
-            else IKGPU_CHAIN_LAUNCH(kMask);
+            if (a.prm.unit_weights) return run_dls_build<NJ, KT, kHot>(ph, dt, io, prm, stream, a);
+            return run_dls_build<NJ, KT, kMask>(ph, dt, io, prm, stream, a);
         }
     }
-    IKGPU_CHAIN_LAUNCH(0);
-#undef IKGPU_CHAIN_LAUNCH
+    return run_dls_build<NJ, KT, 0>(ph, dt, io, prm, stream, a);
 }
 
 template <int NJ, int KT>
@@ -287,32 +240,6 @@ int stop_rule_mode(const ikgpu_dls_params &prm, int64_t B, int64_t resident_wave
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream && hipStreamIsCapturing(stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive) return kStopRefill;
     return kStopTwoPhase;
-}
-
-hipError_t two_phase_begin(QueuePool &queues, const BatchIO &io, hipStream_t stream, unsigned long long *queue, TwoPhase *tp) {
-    if (io.B > 0x7fffffff) return hipErrorInvalidValue;   // (the worklist holds 32-bit problem indices)
-    hipError_t e = hipSuccess;
-    tp->worklist = queues.worklist_for(stream, static_cast<size_t>(io.B), &e);
-    if (!tp->worklist) return e;
-    tp->count = queue + 2;
-    tp->success = io.success;
-    tp->iters = io.iters;
-    if (!tp->success) {
-        if ((e = hipMallocAsync(&tp->tmp[0], static_cast<size_t>(io.B), stream)) != hipSuccess) return e;
-        tp->success = static_cast<uint8_t *>(tp->tmp[0]);
-    }
-    if (!tp->iters) {
-        if ((e = hipMallocAsync(&tp->tmp[1], sizeof(int32_t) * static_cast<size_t>(io.B), stream)) != hipSuccess) return e;
-        tp->iters = static_cast<int32_t *>(tp->tmp[1]);
-    }
-    return hipSuccess;
-}
-
-hipError_t two_phase_end(TwoPhase *tp, hipStream_t stream) {
-    hipError_t e = hipSuccess;
-    for (void *&p : tp->tmp)
-        if (p) { const hipError_t f = hipFreeAsync(p, stream); if (e == hipSuccess) e = f; p = nullptr; }
-    return e;
 }
 
 int64_t refill_resident(int64_t occupancy_waves, int64_t B) {
@@ -415,44 +342,14 @@ hipError_t launch_fk_chain(const ProblemHost &ph, const DeviceTables &dt, int64_
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-using ikdev::LegFactor;
+using ikdev::LdsPark;
 using ikdev::TreeDesc;
 using ikdev::TreeKernelArgs;
 
-// While chain 1 is evaluated, chain 0's factor (L packed, W, u: 77 doubles for NJ = 7) is parked in LDS as
-// [entry][lane]: consecutive lanes hit consecutive 8-byte words, so every ds_write_b64 / ds_read_b64 is
-// conflict-free.  77 x 512 B = 38.5 KB per wave: two waves share a workgroup (and one copy of the constant
-// table) so that four waves -- one per SIMD -- fit the CU's 160 KB of LDS.
+// Chain 0's factor is parked in LDS while chain 1 is evaluated (ikdev::LdsPark, 77 x 512 B = 38.5 KB per wave for NJ = 7): two waves
+// share a workgroup (and one copy of the constant table) so that four waves -- one per SIMD -- fit the CU's 160 KB of LDS.
 constexpr int kTreeWaves = 2;
 constexpr int kTreeBlock = 64 * kTreeWaves;
-
-template <int NJ>
-struct LdsPark {
-    static constexpr int kL = NJ * (NJ + 1) / 2;
-    static constexpr int kEntries = kL + NJ * 6 + NJ;
-    double (*buf)[64];
-    int lane;
-    __device__ __forceinline__ void store(const LegFactor<NJ> &F) const {
-#pragma unroll
-        for (int e = 0; e < kL; ++e) buf[e][lane] = F.L[e];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) buf[kL + j * 6 + c][lane] = F.W[j][c];
-            buf[kL + NJ * 6 + j][lane] = F.u[j];
-        }
-    }
-    __device__ __forceinline__ void load(LegFactor<NJ> &F) const {
-#pragma unroll
-        for (int e = 0; e < kL; ++e) F.L[e] = buf[e][lane];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) F.W[j][c] = buf[kL + j * 6 + c][lane];
-            F.u[j] = buf[kL + NJ * 6 + j][lane];
-        }
-    }
-};
 
 template <int NJ, int NCH>
 __device__ __forceinline__ const TreeDesc<NJ, NCH> &stage_tree_desc(const TreeDesc<NJ, NCH> *src, double *lds, int nthreads) {
@@ -535,10 +432,12 @@ TreeKernelArgs<NJ, NCH> make_tree_args(const ProblemHost &ph, const DeviceTables
 }
 
 }  // namespace
-// kernels_tree_refill.hip
+// kernels_tree_refill.hip: the resident waves of a lock-step build's refill twin (0: it has none), and its launch
 template <int NJ, int NCH>
-bool launch_tree_refill(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream,
-                        ikdev::TreeKernelArgs<NJ, NCH> a, int build, hipError_t *err, unsigned long long *phase2_queue);
+int64_t tree_refill_waves(const ProblemHost &ph, int build, int64_t B);
+template <int NJ, int NCH>
+hipError_t launch_tree_refill_build(const ikdev::TreeKernelArgs<NJ, NCH> &a, int build, int64_t waves, unsigned long long *queue, int chunk,
+                                    hipStream_t stream);
 namespace {
 
 template <int NJ>
@@ -558,13 +457,8 @@ template <int NJ, int NCH>
 hipError_t run_dls_tree(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm,
                         hipStream_t stream, const double *pik_lambda1) {
     TreeKernelArgs<NJ, NCH> a = make_tree_args<NJ, NCH>(ph, dt);
-    a.prm.max_iterations = prm.max_iterations;
-    a.prm.lam2 = prm.damping * prm.damping;
-    a.prm.step_length = prm.step_length;
-    a.prm.stop_sq_tol = prm.stop_sq_tol;
+    fill_solve_args(a, io, prm);
     if (pik_lambda1) { a.prm.pik_on = 1; a.prm.pik_lam2_1 = *pik_lambda1 * *pik_lambda1; }
-    a.layout = io.layout; a.B = io.B; a.q0 = io.q0; a.targets = io.targets;
-    a.q_out = io.q_out; a.success = io.success; a.iters = io.iters;
     // hot build: both chains carry the shape's known placement mask, every task is Full with unit weights and the base
     // task sits at a pure translation from the base joint -- all folded at compile time; otherwise the general build
     constexpr int kMask = HotMask<NJ>::value;
@@ -604,27 +498,20 @@ hipError_t run_dls_tree(const ProblemHost &ph, const DeviceTables &dt, const Bat
     } else if (ph.has_posture)
         IKGPU_TREE_GENERAL((1 << ikdev::kSpecPost), post_lds);
     else IKGPU_TREE_GENERAL(0, 0);
+    return hipGetLastError();
     };
     if constexpr (NCH != 2) {
         if (ph.cons_on && !pik_lambda1 && !hot && !mask_only) return hipErrorInvalidValue;
     }
     // stop-rule mode on a batch larger than the machine: lane refill (kernels_tree_refill.hip) for the builds that have it -- every
     // build without per-lane state outside q (no posture rows, no constraint, no ik::pik level) -- directly, or as the second phase
-    // after the lock-step kernel's first iterations (kernels.hpp stop_rule_mode)
-    if (!pik_lambda1 && !ph.cons_on && !ph.has_posture && prm.stop_sq_tol >= 0.0 && prm.max_iterations >= 1) {
-        hipError_t re = hipSuccess;
-        const int build = hot ? kTreeBuildHot : mask_only ? kTreeBuildMask : fold ? kTreeBuildFold : kTreeBuildGeneral;
-        if (launch_tree_refill<NJ, NCH>(ph, dt, io, prm, stream, a, build, &re, nullptr)) {
-            if (re != hipErrorNotReady) return re;
-            return run_two_phase(dt.queues, io, stream, a, true, launch_lockstep, [&](unsigned long long *queue) {
-                hipError_t pe = hipSuccess;
-                (void)launch_tree_refill<NJ, NCH>(ph, dt, io, prm, stream, a, build, &pe, queue);
-            });
-        }
-    }
-    launch_lockstep();
+    // after the lock-step kernel's first iterations (kernels.hpp run_stop_rule; the never-stop visitor runs lock-step)
+    const int build = hot ? kTreeBuildHot : mask_only ? kTreeBuildMask : fold ? kTreeBuildFold : kTreeBuildGeneral;
+    const int64_t waves = !pik_lambda1 && prm.stop_sq_tol >= 0.0 && prm.max_iterations >= 1 ? tree_refill_waves<NJ, NCH>(ph, build, io.B) : 0;
+    const hipError_t e = run_stop_rule(dt.queues, io, prm, stream, a, true, waves, PassThrough{&ph, &dt}, launch_lockstep,
+                                       [&](unsigned long long *queue, int chunk) { return launch_tree_refill_build<NJ, NCH>(a, build, waves, queue, chunk, stream); });
 #undef IKGPU_TREE_GENERAL
-    return hipGetLastError();
+    return e;
 }
 
 template <int NJ, int NCH>
@@ -1024,12 +911,7 @@ hipError_t launch_dls_generic(const ProblemHost &ph, const DeviceTables &dt, con
         ikdev::CoopKernelArgs c{};
         c.T = bind_generic_tables(ph, dt.g_ints, dt.g_dbls);
         c.L = bind_coop_layout(ph, dt.g_ints);
-        c.prm.max_iterations = prm.max_iterations;
-        c.prm.lam2 = prm.damping * prm.damping;
-        c.prm.step_length = prm.step_length;
-        c.prm.stop_sq_tol = prm.stop_sq_tol;
-        c.layout = io.layout; c.B = io.B; c.q0 = io.q0; c.targets = io.targets;
-        c.q_out = io.q_out; c.success = io.success; c.iters = io.iters;
+        fill_solve_args(c, io, prm);
         const CoopStaging s{dt.g_ints, dt.g_dbls, static_cast<int>(ph.generic.ints.size()), static_cast<int>(ph.generic.dbls.size())};
         const int per_block = ikdev::kCoopPerBlock;  // 4 x 16 lanes = one wave; 2 and 1 problems per workgroup measured slower
         const size_t lds = sizeof(double) * (static_cast<size_t>(per_block) * static_cast<size_t>(c.L.words) +
@@ -1050,16 +932,10 @@ hipError_t launch_dls_generic(const ProblemHost &ph, const DeviceTables &dt, con
         return hipGetLastError();
     }
     ikdev::GenericKernelArgs a{};
-    a.prm.max_iterations = prm.max_iterations;
-    a.prm.lam2 = prm.damping * prm.damping;
-    a.prm.step_length = prm.step_length;
-    a.prm.stop_sq_tol = prm.stop_sq_tol;
+    fill_solve_args(a, io, prm);
     fill_visitor(a.prm, prm);
-    a.layout = io.layout; a.q0 = io.q0; a.targets = io.targets;
-    a.q_out = io.q_out; a.success = io.success; a.iters = io.iters;
     if (!force_lane && generic_runs_in_lds(ph)) {
         a.T = bind_generic_tables(ph, dt.g_ints, dt.g_dbls);
-        a.B = io.B;
         const size_t lds = sizeof(double) * 64 * static_cast<size_t>(ph.generic.ws_words);
         if (!raise_lds_limit(reinterpret_cast<const void *>(dls_generic_lds_kernel), lds)) return hipGetLastError();
         hipLaunchKernelGGL(dls_generic_lds_kernel, dim3(static_cast<unsigned>((io.B + 63) / 64)), dim3(64), lds, stream, a);

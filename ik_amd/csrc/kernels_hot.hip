@@ -55,28 +55,6 @@ static bool chain_hot_eligible(const ProblemHost &ph) {
     return ph.chain_struct.fits;
 }
 
-// A lane-refill launch of a hot build: queue slot, an iteration-count array when the caller passed none, the kernel, then the
-// entries of q outside the chain (kernels.hip launch_chain_pass_through).
-template <int NJ, class LaunchFn>
-static hipError_t hot_refill_launch(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, ChainKernelArgs<NJ> &a, hipStream_t stream, LaunchFn launch) {
-    hipError_t e = hipSuccess;
-    unsigned long long *queue = dt.queues.slot_for(stream, &e);
-    if (!queue) return e;
-    void *tmp = nullptr;
-    if (!a.iters) {
-        if ((e = hipMallocAsync(&tmp, sizeof(int32_t) * static_cast<size_t>(io.B), stream)) != hipSuccess) return e;
-        a.iters = static_cast<int32_t *>(tmp);
-    }
-    launch(queue);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_chain_pass_through(ph, dt, io, a.iters, stream);
-    if (tmp) {
-        const hipError_t f = hipFreeAsync(tmp, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
-}
-
 bool chain_hot_built(const ProblemHost &ph) {
     if (!chain_hot_eligible(ph)) return false;
     const ChainStructure &s = ph.chain_struct;
@@ -110,33 +88,23 @@ hipError_t launch_dls_chain_hot(const ProblemHost &ph, const DeviceTables &dt, c
     if (tab.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
     std::memcpy(t.v, tab.data(), tab.size() * sizeof(double));
     const dim3 grid(static_cast<unsigned>((io.B + kBlock - 1) / kBlock));
-#define X(N, K0, K1, K2)                                                                                                 \
-    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) {                                        \
-        ChainKernelArgs<N> a{};                                                                                          \
-        fill_chain_args(ph, a.ref_pl, a.qidx, a.vidx, &a.nq, &a.nv, &a.prm.priority, &a.prm.idmask, &a.prm.unit_weights); \
-        a.lower = dt.lower; a.upper = dt.upper; a.q_in_chain = dt.q_in_chain;                                            \
-        a.prm.max_iterations = prm.max_iterations;                                                                       \
-        a.prm.lam2 = prm.damping * prm.damping;                                                                          \
-        a.prm.step_length = prm.step_length;                                                                             \
-        a.prm.stop_sq_tol = prm.stop_sq_tol;                                                                             \
-        a.layout = io.layout; a.B = io.B; a.q0 = io.q0; a.targets = io.targets;                                          \
-        a.q_out = io.q_out; a.success = io.success; a.iters = io.iters;                                                  \
-        if (prm.stop_sq_tol < 0.0) hipLaunchKernelGGL((dls_chain_hot_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t); \
-        else {                                                                                                           \
-            const void *rk = reinterpret_cast<const void *>(dls_chain_hot_refill_kernel<N, K0, K1, K2>);                   \
-            const int64_t rgrid = refill_grid(rk, io.B);                                                                 \
-            const int mode = stop_rule_mode(prm, io.B, rgrid, stream, false);                                                  \
-            if (mode == kStopRefill) return hot_refill_launch<N>(ph, dt, io, a, stream, [&](unsigned long long *queue) {  \
-                hipLaunchKernelGGL((dls_chain_hot_refill_kernel<N, K0, K1, K2>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, t, queue, refill_chunk(io.B, rgrid)); \
-            });                                                                                                          \
-            if (mode == kStopTwoPhase) return run_two_phase(dt.queues, io, stream, a, false, [&] {                                    \
-                hipLaunchKernelGGL((dls_chain_hot_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t);    \
-            }, [&](unsigned long long *queue) {                                                                          \
-                hipLaunchKernelGGL((dls_chain_hot_refill_kernel<N, K0, K1, K2>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, t, queue, refill_chunk(io.B, rgrid)); \
-            });                                                                                                          \
+#define X(N, K0, K1, K2)                                                                                                     \
+    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) {                                            \
+        ChainKernelArgs<N> a{};                                                                                              \
+        fill_chain_kernel_args(a, ph, dt);                                                                                   \
+        fill_solve_args(a, io, prm);                                                                                         \
+        if (prm.stop_sq_tol < 0.0) {                                                                                         \
+            hipLaunchKernelGGL((dls_chain_hot_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t);           \
+            return hipGetLastError();                                                                                        \
+        }                                                                                                                    \
+        const int64_t rgrid = refill_grid(reinterpret_cast<const void *>(dls_chain_hot_refill_kernel<N, K0, K1, K2>), io.B); \
+        return run_stop_rule(dt.queues, io, prm, stream, a, false, rgrid, PassThrough{&ph, &dt}, [&] {                       \
             hipLaunchKernelGGL((dls_chain_hot_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t);          \
-        }                                                                                                                \
-        return hipGetLastError();                                                                                        \
+            return hipGetLastError();                                                                                        \
+        }, [&](unsigned long long *queue, int chunk) {                                                                       \
+            hipLaunchKernelGGL((dls_chain_hot_refill_kernel<N, K0, K1, K2>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, t, queue, chunk); \
+            return hipGetLastError();                                                                                        \
+        });                                                                                                                  \
     }
     IKGPU_HOT_SHAPES(X)
 #undef X

@@ -495,6 +495,16 @@ bool module_for(const ProblemHost &ph, HotModule &out, hipError_t *err) {
     return true;
 }
 
+// Resident waves of a run-time compiled refill program: its occupancy x the device's compute units (kernels.hip refill_resident).
+int64_t module_refill_waves(int waves_per_cu, int64_t B) {
+    int cus = 256;
+    {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
+    }
+    return refill_resident(static_cast<int64_t>(waves_per_cu) * cus, B);
+}
+
 template <int NJ>
 hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream,
                         const HotModule &m) {
@@ -506,14 +516,8 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     } args{};
     static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0, "argument layout");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
-    fill_chain_args(ph, a.ref_pl, a.qidx, a.vidx, &a.nq, &a.nv, &a.prm.priority, &a.prm.idmask, &a.prm.unit_weights);
-    a.lower = dt.lower; a.upper = dt.upper; a.q_in_chain = dt.q_in_chain;
-    a.prm.max_iterations = prm.max_iterations;
-    a.prm.lam2 = prm.damping * prm.damping;
-    a.prm.step_length = prm.step_length;
-    a.prm.stop_sq_tol = prm.stop_sq_tol;
-    a.layout = io.layout; a.B = io.B; a.q0 = io.q0; a.targets = io.targets;
-    a.q_out = io.q_out; a.success = io.success; a.iters = io.iters;
+    fill_chain_kernel_args(a, ph, dt);
+    fill_solve_args(a, io, prm);
     if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
     std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
 
@@ -524,41 +528,13 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     };
     const size_t two = offsetof(Args, queue), three = offsetof(Args, chunk) + sizeof(int);
     if (prm.stop_sq_tol < 0.0) return launch(m.never, waves, two);
-    int cus = 256;
-    {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-    }
-    const int64_t resident = refill_resident(static_cast<int64_t>(m.refill_waves_per_cu) * cus, io.B);
-    const int mode = stop_rule_mode(prm, io.B, resident, stream, false);
-    if (mode == kStopLockStep) return launch(m.stop, waves, two);
-    if (mode == kStopTwoPhase) {
-        hipError_t le = hipSuccess;
-        const hipError_t te = run_two_phase(dt.queues, io, stream, a, false, [&] { le = launch(m.stop, waves, two); },
-                                            [&](unsigned long long *queue) {
-                                                args.queue = queue;
-                                                args.chunk = refill_chunk(io.B, resident);
-                                                const hipError_t r = launch(m.refill, resident, three);
-                                                if (le == hipSuccess) le = r;
-                                            });
-        return te != hipSuccess ? te : le;
-    }
-    hipError_t e = hipSuccess;
-    args.queue = dt.queues.slot_for(stream, &e);
-    if (!args.queue) return e;
-    void *tmp = nullptr;
-    if (!a.iters) {
-        if ((e = hipMallocAsync(&tmp, sizeof(int32_t) * static_cast<size_t>(io.B), stream)) != hipSuccess) return e;
-        a.iters = static_cast<int32_t *>(tmp);
-    }
-    args.chunk = refill_chunk(io.B, resident);
-    e = launch(m.refill, resident, three);
-    if (e == hipSuccess) e = launch_chain_pass_through(ph, dt, io, a.iters, stream);
-    if (tmp) {
-        const hipError_t f = hipFreeAsync(tmp, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
+    const int64_t resident = module_refill_waves(m.refill_waves_per_cu, io.B);
+    return run_stop_rule(dt.queues, io, prm, stream, a, false, resident, PassThrough{&ph, &dt}, [&] { return launch(m.stop, waves, two); },
+                         [&](unsigned long long *queue, int chunk) {
+                             args.queue = queue;
+                             args.chunk = chunk;
+                             return launch(m.refill, resident, three);
+                         });
 }
 
 // ---- the generic lane program specialised for ONE problem (device/generic_solver.hpp with IKD_STATIC_TABLES) -----------------------
@@ -994,7 +970,7 @@ bool rtc_generic_static_precompile_refill(const ProblemHost &gen) {   // (compil
 }
 
 hipError_t rtc_launch_generic_static(const ProblemHost &gen, uint64_t key, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream,
-                                     QueuePool *queues) {
+                                     QueuePool &queues) {
     struct Args {
         ikdev::GenericKernelArgs a;
         unsigned long long *queue;
@@ -1002,16 +978,11 @@ hipError_t rtc_launch_generic_static(const ProblemHost &gen, uint64_t key, const
     } args{};
     static_assert(sizeof(ikdev::GenericKernelArgs) % 8 == 0, "argument layout");
     ikdev::GenericKernelArgs &a = args.a;
-    a.prm.max_iterations = prm.max_iterations;
-    a.prm.lam2 = prm.damping * prm.damping;
-    a.prm.step_length = prm.step_length;
-    a.prm.stop_sq_tol = prm.stop_sq_tol;
+    fill_solve_args(a, io, prm);
     fill_visitor(a.prm, prm);
-    a.layout = io.layout; a.B = io.B; a.q0 = io.q0; a.targets = io.targets;
-    a.q_out = io.q_out; a.success = io.success; a.iters = io.iters;
     // stop-rule mode on a batch larger than the machine: lane refill (as the chain and tree kernels; `refill_wanted` is false at or
-    // below one wave per SIMD, so the small-batch path never meets the compiler here)
-    const bool maybe_refill = queues && refill_wanted(prm, io.B, 1024);
+    // below one wave per SIMD, so the small-batch path never meets the compiler here, and the mode stays lock-step)
+    const bool maybe_refill = refill_wanted(prm, io.B, 1024);
     GenModule m;
     const HotCode *refill_obj = nullptr;
     for (int pass = 0;; ++pass) {
@@ -1034,35 +1005,15 @@ hipError_t rtc_launch_generic_static(const ProblemHost &gen, uint64_t key, const
         void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(fn, static_cast<unsigned>(grid), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
     };
-    if (maybe_refill && m.refill) {
-        int cus = 256;
-        {
-            int dev = 0, n = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-        }
-        const int64_t resident = refill_resident(static_cast<int64_t>(m.refill_waves_per_cu) * cus, io.B);
-        // (the switch point of the tree kernels: a static lane program is as heavy, one wave per SIMD in many rounds -- kernels.hpp)
-        const int mode = stop_rule_mode(prm, io.B, resident, stream, true);
-        if (mode == kStopRefill) {
-            hipError_t e = hipSuccess;
-            args.queue = queues->slot_for(stream, &e);
-            if (!args.queue) return e;
-            args.chunk = refill_chunk(io.B, resident);
-            return launch(m.refill, resident, offsetof(Args, chunk) + sizeof(int));
-        }
-        if (mode == kStopTwoPhase) {   // (kernels.hpp run_two_phase: the lock-step program until a wave's stragglers are few, the refill twin on those)
-            hipError_t le = hipSuccess;
-            const hipError_t te = run_two_phase(*queues, io, stream, a, true, [&] { le = launch(m.dls, (io.B + 63) / 64, sizeof(ikdev::GenericKernelArgs)); },
-                                                [&](unsigned long long *queue) {
-                                                    args.queue = queue;
-                                                    args.chunk = refill_chunk(io.B, resident);
-                                                    const hipError_t r = launch(m.refill, resident, offsetof(Args, chunk) + sizeof(int));
-                                                    if (le == hipSuccess) le = r;
-                                                });
-            return le != hipSuccess ? le : te;
-        }
-    }
-    return launch(m.dls, (io.B + 63) / 64, sizeof(ikdev::GenericKernelArgs));
+    // (the switch point of the tree kernels: a static lane program is as heavy, one wave per SIMD in many rounds -- kernels.hpp)
+    const int64_t resident = maybe_refill && m.refill ? module_refill_waves(m.refill_waves_per_cu, io.B) : 0;
+    return run_stop_rule(queues, io, prm, stream, a, true, resident, PassThrough{},
+                         [&] { return launch(m.dls, (io.B + 63) / 64, sizeof(ikdev::GenericKernelArgs)); },
+                         [&](unsigned long long *queue, int chunk) {
+                             args.queue = queue;
+                             args.chunk = chunk;
+                             return launch(m.refill, resident, offsetof(Args, chunk) + sizeof(int));
+                         });
 }
 
 }  // namespace ikgpu

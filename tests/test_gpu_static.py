@@ -158,7 +158,7 @@ def test_static_program_lane_refill_is_bit_identical_to_lock_step(torch_cuda, mo
             Q0 = torch.from_numpy(np.ascontiguousarray(q)).cuda()
             T = torch.from_numpy(np.ascontiguousarray(t)).cuda()
         res = {}
-        # "2": the two-phase solve (kernels.hpp run_two_phase: the lock-step program until a wave's stragglers are few, the refill twin
+        # "2": the two-phase solve (kernels.hpp run_stop_rule: the lock-step program until a wave's stragglers are few, the refill twin
         # on the problems left open), also with the hand-over at once and late; None: the default policy for this batch size
         for mode, env in (("0", {}), ("1", {}), ("2", {}), ("2 at once", {"IKGPU_TWO_PHASE_ITERS": "1", "IKGPU_TWO_PHASE_ACTIVE": "63"}),
                           ("2 late", {"IKGPU_TWO_PHASE_ITERS": "12", "IKGPU_TWO_PHASE_ACTIVE": "2"}), (None, {})):

@@ -1,5 +1,5 @@
 """Lane refill of the free-flyer tree kernels (device/tree_kernel_body.hpp TreeRefill, kernels_tree_refill.hip): what a stop-rule solve
-of a tree problem runs BY DEFAULT once the batch exceeds the lanes the device keeps resident (kernels.hip refill_wanted).  A lane whose
+of a tree problem runs BY DEFAULT once the batch exceeds the lanes the device keeps resident (kernels.hpp stop_rule_mode).  A lane whose
 visitor fired (reference ik/ik/visitor.hpp:15-21, ik/ik/dls.cpp:61-64) or whose count reached max_iterations (dls.cpp:76-77) stores
 its result and takes the next unsolved problem; the rest of q is clipped afterwards by the pass-through kernel (common.hpp:53-56).
 

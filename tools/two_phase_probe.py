@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The two-phase stop-rule solve (kernels.hpp run_two_phase) by its two switch parameters -- K (iterations before a wave of the first
+"""The two-phase stop-rule solve (kernels.hpp run_stop_rule) by its two switch parameters -- K (iterations before a wave of the first
 phase may leave) and N (it leaves with <= N lanes still iterating) -- next to the two fixed modes, on the Cassie leg or ("tree") the
 full body; every result compared bit for bit with the lock-step kernel's.
     python tools/two_phase_probe.py [tree]     the table
