@@ -565,6 +565,59 @@ def dls_batch(problem, Q0, targets, data, visitor=None, p=None, layout="soa", ou
     return Q, ok, it
 
 
+def dls_track_kernel(data, visitor=None, p=None):
+    """Name of what dls_track_batch runs for these parameters: "dls_chain_track<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_track_kernel(data._h, C.byref(prm)).decode()
+
+
+def dls_track_batch(problem, Q0, targets, data, visitor=None, p=None, layout="soa", out=None, stream=None):
+    """B trajectories of T waypoints: waypoint k of every problem is solved from the result of waypoint k - 1 (waypoint 0 from Q0) --
+    the reference caller's tick loop (ik_ros/src/cassie.cpp:92-113) as a horizon.  Bit-identical to T chained dls_batch calls; a
+    chain problem runs the whole sequence in one launch with q on-chip between waypoints.
+
+    float64 CUDA tensors, contiguous, waypoints outermost:
+      layout "soa": Q0 [nq, B], targets [T, ntasks, 12, B]   |   "aos": Q0 [B, nq], targets [T, B, ntasks, 12]
+    out: (Q [T, nq, B] | [T, B, nq], success uint8 [T, B], iterations int32 [T, B]) preallocated, or None.
+    Returns (Q, success, iterations)."""
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
+    if len(Q0.shape) != 2 or len(targets.shape) != 4:
+        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 4 dimensions (waypoints outermost)" % (tuple(Q0.shape), tuple(targets.shape)))
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    T = targets.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(targets.shape[1:]), model.nq, ntasks, B, lay)
+    if not (isinstance(Q0, torch.Tensor) and isinstance(targets, torch.Tensor) and Q0.is_cuda and targets.is_cuda
+            and Q0.dtype == torch.float64 and targets.dtype == torch.float64):
+        raise TypeError("dls_track_batch needs float64 CUDA tensors")
+    if not (Q0.is_contiguous() and targets.is_contiguous()):
+        raise ValueError("dls_track_batch needs contiguous tensors")
+    if Q0.device.index != data._device or targets.device.index != data._device:
+        raise ValueError("tensors live on cuda:%s / cuda:%s but the problem was created on device %d"
+                         % (Q0.device.index, targets.device.index, data._device))
+    q_shape = (T, model.nq, B) if lay == capi.SOA else (T, B, model.nq)
+    if out is None:
+        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
+        ok = torch.empty((T, B), dtype=torch.uint8, device=Q0.device)
+        it = torch.empty((T, B), dtype=torch.int32, device=Q0.device)
+    else:
+        Q, ok, it = out
+        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
+        _check_tensor("out[1] (success)", ok, (T, B), torch.uint8, data._device)
+        _check_tensor("out[2] (iterations)", it, (T, B), torch.int32, data._device)
+    data._bind(problem)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(capi.lib().ikgpu_dls_track_batch(data._h, B, T, Q0.data_ptr(), targets.data_ptr(), C.byref(prm), Q.data_ptr(),
+                                                ok.data_ptr(), it.data_ptr(), lay, C.c_void_p(s)))
+    return Q, ok, it
+
+
 def _check_tensor(name, t, shape, dtype, device):
     """A device buffer handed to the C ABI as a raw pointer: wrong dtype / device / stride / size would make the kernel read or
     write out of bounds, so it is refused here."""

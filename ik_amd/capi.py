@@ -34,6 +34,7 @@ SYMBOLS = [
     "ikgpu_shard_group_size", "ikgpu_shard_group_problem", "ikgpu_shard_group_uses_rccl", "ikgpu_shard_group_stream",
     "ikgpu_shard_group_last_issue_us",
     "ikgpu_dls_solve_batch_sharded", "ikgpu_shard_group_synchronize", "ikgpu_targets_from_pose7",
+    "ikgpu_dls_track_batch", "ikgpu_dls_track_kernel",
 ]
 MAX_PIK_LEVELS, MAX_PIK_DA = 8, 128
 
@@ -141,6 +142,10 @@ def lib():
     L.ikgpu_targets_from_pose7.argtypes = [i64, i32, vp, vp, C.c_int, vp]
     L.ikgpu_dls_solve_batch.argtypes = [vp, i64, vp, vp, C.POINTER(DlsParams), vp, vp, vp, C.c_int, vp]
     L.ikgpu_dls_solve_batch_host.argtypes = [vp, i64, vp, vp, C.POINTER(DlsParams), vp, vp, vp, C.c_int]
+    L.ikgpu_dls_track_batch.argtypes = [vp, i64, i64, vp, vp, C.POINTER(DlsParams), vp, vp, vp, C.c_int, vp]
+    L.ikgpu_dls_track_batch.restype = C.c_int
+    L.ikgpu_dls_track_kernel.argtypes = [vp, C.POINTER(DlsParams)]
+    L.ikgpu_dls_track_kernel.restype = C.c_char_p
     L.ikgpu_pik_params_default.argtypes = [C.POINTER(PikParams), i32]
     L.ikgpu_pik_params_default.restype = None
     L.ikgpu_pik_solve_batch.argtypes = [vp, i64, vp, vp, C.POINTER(PikParams), vp, vp, vp, C.c_int, vp]

@@ -408,6 +408,10 @@ int host_solve(const ikgpu_problem *p, int64_t B, const double *q0, const double
 
 }  // namespace
 
+namespace {
+int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_dls_params *params, hipStream_t st);
+}
+
 extern "C" {
 
 int ikgpu_abi_version(void) { return IKGPU_ABI_VERSION; }
@@ -677,28 +681,93 @@ int ikgpu_dls_solve_batch(const ikgpu_problem *p, int64_t B, const double *q0, c
     return guarded([&] {
         DeviceGuard g(p->device);
         if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
+        return dispatch_dls(p, ikgpu::BatchIO{B, q0, targets, q_out, success, iters, layout}, params, static_cast<hipStream_t>(stream));
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// The kernel dispatch of ikgpu_dls_solve_batch for validated arguments, on the problem's device, inside `guarded` (the launchers
+// throw for a shape without an instantiation).  ikgpu_dls_track_batch loops over it for the problem kinds without a tracking kernel.
+int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_dls_params *params, hipStream_t st) {
+    if (ikgpu::visitor_extended(*params)) {
+        // a derived visitor (step tolerance / per-level tolerances): the generic lane program implements the family -- the one
+        // specialised for this problem when there is one, else its memory-resident per-lane form
+        if (p->gen.generic_build != 2)
+            std::call_once(p->visitor_static_once, [&] {
+                p->visitor_static = ikgpu::rtc_generic_static_available(p->gen, /*compile=*/true, &p->visitor_static_key);
+            });
+        const bool on_static = p->gen.generic_build == 2 || p->visitor_static;
+        const uint64_t key = p->gen.generic_build == 2 ? p->gen.generic_key : p->visitor_static_key;
+        const hipError_t ev = on_static ? ikgpu::rtc_launch_generic_static(p->gen, key, io, *params, st, p->dev.queues)
+                                        : ikgpu::launch_dls_generic(p->gen, p->dev, io, *params, st, /*force_lane=*/true);
+        if (ev != hipSuccess) return hip_fail(ev, "launching the generic DLS kernel (derived visitor)");
+        return static_cast<int>(IKGPU_OK);
+    }
+    hipError_t e = p->dls_on_static_gen                      ? ikgpu::rtc_launch_generic_static(p->gen, p->gen.generic_key, io, *params, st, p->dev.queues)
+                   : p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_dls_chain(p->host, p->dev, io, *params, st)
+                   : p->host.kind == ikgpu::KernelKind::Tree ? ikgpu::launch_dls_tree(p->host, p->dev, io, *params, st)
+                   : p->host.generic_build == 2              ? ikgpu::rtc_launch_generic_static(p->host, p->host.generic_key, io, *params, st, p->dev.queues)
+                                                             : ikgpu::launch_dls_generic(p->host, p->dev, io, *params, st);
+    if (e != hipSuccess) return hip_fail(e, "launching the DLS kernel");
+    return static_cast<int>(IKGPU_OK);
+}
+
+// A chain problem under the reference's own visitor has a tracking kernel: one launch for the whole sequence.
+bool track_is_fused(const ikgpu_problem *p, const ikgpu_dls_params *params) {
+    return p->host.kind == ikgpu::KernelKind::Chain && !p->dls_on_static_gen && !ikgpu::visitor_extended(*params);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *ikgpu_dls_track_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    if (track_is_fused(p, params)) {   // "dls_chain<NJ=7,full,hot>" -> "dls_chain_track<NJ=7,full,hot>"
+        const size_t lt = p->dls_name.find('<');
+        name = p->dls_name.substr(0, lt) + "_track" + (lt == std::string::npos ? "" : p->dls_name.substr(lt));
+    } else {
+        name = "loop(" + p->dls_name + ")";
+    }
+    return name.c_str();
+}
+
+int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *targets,
+                          const ikgpu_dls_params *params, double *q_traj, uint8_t *success, int32_t *iters, int layout,
+                          void *stream) {
+    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
+    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (T < 0) return fail(IKGPU_ERR_INVALID, "negative number of waypoints");
+    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_params(params)) return rc;
+    if (B == 0 || T == 0) return IKGPU_OK;  // nothing to solve (the pointers may be null; the problem is not looked at)
+    if (!q0 || !targets || !q_traj) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (B > (int64_t(1) << 31) * 32) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
+    if (T > 0x7fffffff) return fail(IKGPU_ERR_INVALID, "too many waypoints for one call");
+    return guarded([&] {
+        DeviceGuard g(p->device);
+        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
         const hipStream_t st = static_cast<hipStream_t>(stream);
-        if (ikgpu::visitor_extended(*params)) {
-            // a derived visitor (step tolerance / per-level tolerances): the generic lane program implements the family -- the one
-            // specialised for this problem when there is one, else its memory-resident per-lane form
-            if (p->gen.generic_build != 2)
-                std::call_once(p->visitor_static_once, [&] {
-                    p->visitor_static = ikgpu::rtc_generic_static_available(p->gen, /*compile=*/true, &p->visitor_static_key);
-                });
-            const bool on_static = p->gen.generic_build == 2 || p->visitor_static;
-            const uint64_t key = p->gen.generic_build == 2 ? p->gen.generic_key : p->visitor_static_key;
-            const hipError_t ev = on_static ? ikgpu::rtc_launch_generic_static(p->gen, key, io, *params, st, p->dev.queues)
-                                            : ikgpu::launch_dls_generic(p->gen, p->dev, io, *params, st, /*force_lane=*/true);
-            if (ev != hipSuccess) return hip_fail(ev, "launching the generic DLS kernel (derived visitor)");
+        if (track_is_fused(p, params)) {
+            const ikgpu::BatchIO io{B, q0, targets, q_traj, success, iters, layout};
+            const hipError_t e = ikgpu::launch_dls_chain_track(p->host, p->dev, io, static_cast<int>(T), *params, st);
+            if (e != hipSuccess) return hip_fail(e, "launching the DLS tracking kernel");
             return static_cast<int>(IKGPU_OK);
         }
-        hipError_t e = p->dls_on_static_gen                      ? ikgpu::rtc_launch_generic_static(p->gen, p->gen.generic_key, io, *params, st, p->dev.queues)
-                       : p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_dls_chain(p->host, p->dev, io, *params, st)
-                       : p->host.kind == ikgpu::KernelKind::Tree ? ikgpu::launch_dls_tree(p->host, p->dev, io, *params, st)
-                       : p->host.generic_build == 2              ? ikgpu::rtc_launch_generic_static(p->host, p->host.generic_key, io, *params, st, p->dev.queues)
-                                                                 : ikgpu::launch_dls_generic(p->host, p->dev, io, *params, st);
-        if (e != hipSuccess) return hip_fail(e, "launching the DLS kernel");
+        // every other kind: the chained calls themselves, on the same stream
+        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B, t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
+        for (int64_t k = 0; k < T; ++k) {
+            const ikgpu::BatchIO io{B, k == 0 ? q0 : q_traj + (k - 1) * q_slab, targets + k * t_slab, q_traj + k * q_slab,
+                                    success ? success + k * B : nullptr, iters ? iters + k * B : nullptr, layout};
+            if (const int rc = dispatch_dls(p, io, params, st)) {
+                g_last_error = "waypoint " + std::to_string(k) + ": " + g_last_error;
+                return rc;
+            }
+        }
         return static_cast<int>(IKGPU_OK);
     });
 }

@@ -298,7 +298,7 @@ IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const 
 // every load of a group issued before its first store: one entry per pass (load, wait, store; the next load cannot move above a
 // store that might alias it) cost one HBM round trip per entry -- nine for a Cassie leg, ~10 us of a 150 us launch.
 template <int NJ>
-IKD_FN void hot_pass_through(const ChainKernelArgs<NJ> &a, int64_t b, bool stepped) {
+IKD_FN void hot_pass_through_to(const ChainKernelArgs<NJ> &a, double *q_out, int64_t b, bool stepped) {
     constexpr int kGroup = 16;   // (a Cassie model's sixteen entries in ONE pass: with groups of eight the second group's loads waited
                                  // for the first group's stores -- a second HBM round trip in the prologue)
     for (int i0 = 0; i0 < a.nq; i0 += kGroup) {
@@ -315,10 +315,12 @@ IKD_FN void hot_pass_through(const ChainKernelArgs<NJ> &a, int64_t b, bool stepp
 #pragma unroll
         for (int k = 0; k < kGroup; ++k) {
             const double c = dmin(hi[k], dmax(v[k], lo[k]));
-            if (out[k]) a.q_out[at(a.layout, a.B, a.nq, i0 + k, b)] = stepped ? c : v[k];
+            if (out[k]) q_out[at(a.layout, a.B, a.nq, i0 + k, b)] = stepped ? c : v[k];
         }
     }
 }
+template <int NJ>
+IKD_FN void hot_pass_through(const ChainKernelArgs<NJ> &a, int64_t b, bool stepped) { hot_pass_through_to(a, a.q_out, b, stepped); }
 
 #if IKD_HIP_LANG
 // The hot program under lane refill (chain_kernel_body.hpp chain_refill_loop): the stop-rule mode for batches larger than the machine.
@@ -396,6 +398,46 @@ IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t g
     if (a.iters) a.iters[b] = iters;
 }
 
+// T chained solves of lane `gid`'s problem with q in registers between them -- dls_chain_track_body (chain_kernel_body.hpp: the
+// definition, the slab layout, the rule for the entries outside the chain) with the hot program.  The raw target of waypoint k + 1
+// is in flight during the iteration loop of waypoint k and composed after it: twelve doubles parked, nothing of them in the loop.
+template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
+IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, int64_t gid, AnyFn any_active) {
+    const bool valid = gid < a.B;
+    const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
+    double q[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    // Order per waypoint: solve k, compose target k + 1 (its loads were issued before solve k began), store slab k, THEN issue the loads
+    // of target k + 2.  The wait that consumes a prefetched target therefore never has a store of this waypoint in front of it (loads
+    // and stores share one counter on gfx950: behind a store the wait would be for the store's acknowledgement, once per waypoint).
+    double next[12], oMt[12];
+    if (T > 0) {
+        load_target_raw(a, a.targets, b, next);
+        compose_target(a, next, oMt);
+    }
+    if (T > 1) load_target_raw(a, a.targets + t_slab, b, next);
+    bool stepped = NEVERSTOP && a.prm.max_iterations > 0;   // (never-stop: every waypoint takes max_iterations steps, known here)
+    for (int k = 0; k < T; ++k) {
+        double *q_out = a.q_out + k * q_slab;
+        if (NEVERSTOP && valid) hot_pass_through_to(a, q_out, b, stepped);   // the stores drain while the loop runs (hot_chain_body)
+        int iters;
+        bool success;
+        hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);   // (any_active by value: a fresh count per waypoint)
+        stepped = stepped || iters > 0;
+        if (k + 1 < T) compose_target(a, next, oMt);
+        if (valid) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+            if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
+            if (a.iters) a.iters[k * a.B + b] = iters;
+            if (!NEVERSTOP) hot_pass_through_to(a, q_out, b, stepped);
+        }
+        if (k + 2 < T) load_target_raw(a, a.targets + (k + 2) * t_slab, b, next);
+    }
+}
+
 #if IKD_HIP_LANG
 // ---- kernel entries, shared by the instantiations compiled into the library (kernels_hot.hip) and the ones compiled at run time for
 // a chain's own structure code (rtc.cpp) -----------------------------------------------------------------------------------------
@@ -426,6 +468,14 @@ __device__ __forceinline__ void hot_kernel_entry(const ChainKernelArgs<NJ> &a, c
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
     hot_chain_body<NJ, S, NEVERSTOP>(a, tv, gid, KeepGoing{a.leave_active, a.leave_after, 0});
+}
+
+template <int NJ, class S, bool NEVERSTOP>
+__device__ __forceinline__ void hot_track_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, int T) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
+    HotTable tv;
+    hot_park_table<NJ, S>(t, tv);
+    hot_track_body<NJ, S, NEVERSTOP>(a, tv, T, gid, KeepGoing{0, 0, 0});
 }
 
 template <int NJ, class S>

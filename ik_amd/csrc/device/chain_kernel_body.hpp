@@ -113,6 +113,73 @@ IKD_FN void dls_chain_body(const ChainKernelArgs<NJ> &a, const Desc &d, int64_t 
     if (a.iters) a.iters[b] = iters;
 }
 
+// ---- tracking: a SEQUENCE of T targets per problem in one launch (include/ikgpu.h ikgpu_dls_track_batch) ---------------------------
+// Defined as T calls of the single solve, each started from the result of the one before (the reference's caller does exactly that,
+// ik_ros/src/cassie.cpp:92-113: q_ = ik::dls(*ik_, q_, ...) on every tick).  Waypoints are outermost: slab k of targets / q_out /
+// success / iters is what the single solve takes, so `a` holds the pointers of slab 0 and the strides below lead to slab k.
+// load_target in two halves, so that the twelve loads of a later waypoint can be in flight during the iteration loop of waypoint k and
+// consumed after it: the same expressions, the same bits.
+template <int NJ>
+IKD_FN void load_target_raw(const ChainKernelArgs<NJ> &a, const double *targets, int64_t b, double (&t)[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) t[k] = targets[at(a.layout, a.B, 12, k, b)];
+}
+template <int NJ>
+IKD_FN void compose_target(const ChainKernelArgs<NJ> &a, const double (&t)[12], double (&oMt)[12]) {
+    const double *r = a.ref_pl;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            oMt[3 * i + j] = dfma(r[3 * i], t[j], dfma(r[3 * i + 1], t[3 + j], r[3 * i + 2] * t[6 + j]));
+        oMt[9 + i] = dfma(r[3 * i], t[9], dfma(r[3 * i + 1], t[10], dfma(r[3 * i + 2], t[11], r[9 + i])));
+    }
+}
+
+// T chained ik::dls() calls of lane `gid`'s problem with q on-chip between them.  The wave moves to the next waypoint when its last
+// lane has stopped (any_active, a fresh copy per waypoint: lock-step per solve, as dls_chain_body).  Entries of q outside the chain:
+// call k of the chain writes iters_k > 0 ? clip(previous) : previous, and clipping is idempotent, so slab k holds
+// stepped ? clip(q0[i]) : q0[i] with stepped = "some waypoint <= k took a step" -- read from q0 only, never from an earlier slab.
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN void dls_chain_track_body(const ChainKernelArgs<NJ> &a, const Desc &d, int T, int64_t gid, AnyFn any_active) {
+    const bool valid = gid < a.B;
+    const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
+
+    double q[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    // (order per waypoint: solve k, compose target k + 1, store slab k, issue the loads of target k + 2 -- see hot_track_body)
+    double next[12], oMt[12];
+    if (T > 0) {
+        load_target_raw(a, a.targets, b, next);
+        compose_target(a, next, oMt);
+    }
+    if (T > 1) load_target_raw(a, a.targets + t_slab, b, next);
+    bool stepped = false;
+    for (int k = 0; k < T; ++k) {
+        int iters;
+        bool success;
+        chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active);   // (any_active by value: a fresh count per waypoint)
+        stepped = stepped || iters > 0;
+        if (k + 1 < T) compose_target(a, next, oMt);
+        if (valid) {
+            double *q_out = a.q_out + k * q_slab;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+            if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
+            if (a.iters) a.iters[k * a.B + b] = iters;
+            for (int i = 0; i < a.nq; ++i) {
+                if (a.q_in_chain[i]) continue;
+                const double v = a.q0[at(a.layout, a.B, a.nq, i, b)];
+                const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
+                q_out[at(a.layout, a.B, a.nq, i, b)] = stepped ? c : v;
+            }
+        }
+        if (k + 2 < T) load_target_raw(a, a.targets + (k + 2) * t_slab, b, next);
+    }
+}
+
 #if IKD_HIP_LANG
 // ---- lane refill: the stop-rule mode without lock-step divergence ----------------------------------------------------------------
 // With the reference's default visitor (ik/ik/visitor.hpp:15-21) a problem stops after a handful of iterations or never

@@ -689,6 +689,20 @@ inline void dls_batch_device(InverseKinematicsProblem &problem, std::int64_t B, 
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// B trajectories of T waypoints on DEVICE buffers: waypoint k of every problem starts from the result of waypoint k - 1 (waypoint 0
+// from Q0) -- the caller's tick loop (ik_ros/src/cassie.cpp:92-113: q_ = ik::dls(*ik_, q_, ...)) as a horizon, bit-identical to T
+// chained dls_batch_device calls; a chain problem runs it in one launch.  Waypoints outermost: targets [T][ntasks][12][B],
+// Q [T][nq][B], success / iterations [T][B] (may be null); asynchronous on `stream`.
+inline void dls_track_device(InverseKinematicsProblem &problem, std::int64_t B, std::int64_t T, const number_t *Q0, const number_t *targets,
+                             dls_data &data, number_t *Q, std::uint8_t *success, std::int32_t *iterations, void *stream,
+                             const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                             const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_track_batch(data.handle(), B, T, Q0, targets, &prm, Q, success, iterations, IKGPU_SOA, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // ---- ik::pik, the prioritised solver (ik/ik/pik.hpp:11-59; ik/ik/pik.cpp:31-103) ---------------------
 struct pik_parameters {  // ik/ik/pik.hpp:11-16; the reference loop reads neither damping nor max_time
     int max_iterations = 100;

@@ -68,6 +68,15 @@ __global__ __launch_bounds__(kBlock) void dls_chain_refill_kernel(const ChainKer
     ikdev::dls_chain_refill_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, queue, chunk);
 }
 
+// T chained solves per problem in one launch (device/chain_kernel_body.hpp dls_chain_track_body): the general build's tracking kernel,
+// with the placement mask / weights build (SMASK) the single solve of the same problem takes, so that the bits are the same.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_track_kernel(const ChainKernelArgs<NJ> a, const int T) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    ikdev::dls_chain_track_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, T, gid, ikdev::KeepGoing{0, 0, 0});
+}
+
 struct PassThroughArgs {
     const double *q0, *lower, *upper;
     const uint8_t *q_in_chain;
@@ -143,6 +152,23 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         }
     }
     return run_dls_build<NJ, KT, 0>(ph, dt, io, prm, stream, a);
+}
+
+template <int NJ, int KT>
+hipError_t run_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm, hipStream_t stream) {
+    ChainKernelArgs<NJ> a = make_args<NJ>(ph, dt);
+    fill_solve_args(a, io, prm);
+    constexpr int kMask = HotMask<NJ>::value;   // the build run_dls picks for this problem
+    constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
+    if constexpr (kMask != 0) {
+        if ((a.prm.idmask & kMask) == kMask) {
+            if (a.prm.unit_weights) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, kHot>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
+            else hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, kMask>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, 0>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
+    return hipGetLastError();
 }
 
 template <int NJ, int KT>
@@ -304,6 +330,21 @@ hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const
         if (type == IKGPU_FULL) return run_dls<N, ikdev::KT_FULL>(ph, dt, io, prm, stream);               \
         if (type == IKGPU_POSITION) return run_dls<N, ikdev::KT_POSITION>(ph, dt, io, prm, stream);       \
         if (type == IKGPU_ORIENTATION) return run_dls<N, ikdev::KT_ORIENTATION>(ph, dt, io, prm, stream); \
+    }
+    IKGPU_FOR_NJ(X)
+#undef X
+    not_built(nj, type);
+}
+
+hipError_t launch_dls_chain_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
+                                  hipStream_t stream) {
+    if (ph.chain_build != 0) return launch_dls_chain_hot_track(ph, dt, io, T, prm, stream);
+    const int nj = ph.chain.nj, type = ph.tasks[0].type;
+#define X(N)                                                                                                   \
+    if (nj == N) {                                                                                             \
+        if (type == IKGPU_FULL) return run_track<N, ikdev::KT_FULL>(ph, dt, io, T, prm, stream);               \
+        if (type == IKGPU_POSITION) return run_track<N, ikdev::KT_POSITION>(ph, dt, io, T, prm, stream);       \
+        if (type == IKGPU_ORIENTATION) return run_track<N, ikdev::KT_ORIENTATION>(ph, dt, io, T, prm, stream); \
     }
     IKGPU_FOR_NJ(X)
 #undef X

@@ -70,6 +70,16 @@ hipError_t launch_eval_chain(const ProblemHost &ph, const DeviceTables &dt, int6
                              double *e_out, double *J_out, int layout, hipStream_t stream);
 hipError_t launch_fk_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, const double *q, double *oMf_out, int layout,
                            hipStream_t stream);
+// T chained solves per problem in ONE launch, q on-chip between them (ikgpu_dls_track_batch; device/chain_kernel_body.hpp
+// dls_chain_track_body, device/chain_hot.hpp hot_track_body): `io` holds the pointers of waypoint 0, waypoint k's slab of targets /
+// q_out / success / iters follows at k times the slab's size.  Chain problems only, in the build the single solve takes (general /
+// hot / run-time compiled hot); always lock-step per waypoint, so the launch needs no queue slot and is capturable.
+hipError_t launch_dls_chain_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
+                                  hipStream_t stream);
+hipError_t launch_dls_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
+                                      hipStream_t stream);
+hipError_t rtc_launch_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
+                                      hipStream_t stream);
 bool chain_shape_built(int nj, int type);
 // The structure-specialised builds of the chain kernel (kernels_hot.hip, device/chain_hot.hpp): one Full task with unit
 // weights on a chain whose placement-structure code has an instantiation.  launch_dls_chain takes that route when it exists.

@@ -122,7 +122,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 // values: non-structural placement entries of the chain.  The refill kernel asks for two waves per SIMD (256 registers) unless the
 // parked table alone would take most of them.
 std::string hot_source(int nj, const uint64_t code[3], int values) {
-    char buf[2048];
+    char buf[4096];
     const char *refill_bounds = values <= 40 ? "__launch_bounds__(64, 2)" : "__launch_bounds__(64)";
     std::snprintf(buf, sizeof buf,
                   "#include \"chain_hot.hpp\"\n"
@@ -132,9 +132,14 @@ std::string hot_source(int nj, const uint64_t code[3], int values) {
                   "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t) {\n"
                   "    ikdev::hot_kernel_entry<%d, S, false>(a, t);\n}\n"
                   "extern \"C\" __global__ %s void ikgpu_hot_refill(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, unsigned long long *queue, int chunk) {\n"
-                  "    ikdev::hot_refill_entry<%d, S>(a, t, queue, chunk);\n}\n",
+                  "    ikdev::hot_refill_entry<%d, S>(a, t, queue, chunk);\n}\n"
+                  // T chained solves in one launch (ikgpu_dls_track_batch)
+                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_track_never(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const int T) {\n"
+                  "    ikdev::hot_track_entry<%d, S, true>(a, t, T);\n}\n"
+                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_track_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const int T) {\n"
+                  "    ikdev::hot_track_entry<%d, S, false>(a, t, T);\n}\n",
                   static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]),
-                  nj, nj, nj, nj, refill_bounds, nj, nj);
+                  nj, nj, nj, nj, refill_bounds, nj, nj, nj, nj, nj, nj);
     return buf;
 }
 
@@ -217,7 +222,7 @@ struct HotCode {
 };
 struct HotModule {
     hipModule_t mod = nullptr;
-    hipFunction_t never = nullptr, stop = nullptr, refill = nullptr;
+    hipFunction_t never = nullptr, stop = nullptr, refill = nullptr, track_never = nullptr, track_stop = nullptr;
     int refill_waves_per_cu = 0;
 };
 
@@ -484,6 +489,8 @@ bool module_for(const ProblemHost &ph, HotModule &out, hipError_t *err) {
         if (e == hipSuccess) e = hipModuleGetFunction(&m.never, m.mod, "ikgpu_hot_never");
         if (e == hipSuccess) e = hipModuleGetFunction(&m.stop, m.mod, "ikgpu_hot_stop");
         if (e == hipSuccess) e = hipModuleGetFunction(&m.refill, m.mod, "ikgpu_hot_refill");
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.track_never, m.mod, "ikgpu_hot_track_never");
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.track_stop, m.mod, "ikgpu_hot_track_stop");
         if (e == hipSuccess) {
             int per_cu = 0;
             if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.refill, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
@@ -535,6 +542,27 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
                              args.chunk = chunk;
                              return launch(m.refill, resident, three);
                          });
+}
+
+// The tracking kernel of the same module: (ChainKernelArgs<NJ> a, HotTable t, int T), one launch.
+template <int NJ>
+hipError_t launch_track_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
+                              hipStream_t stream, const HotModule &m) {
+    struct Args {
+        ikdev::ChainKernelArgs<NJ> a;
+        ikdev::HotTable t;
+        int T;
+    } args{};
+    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0, "argument layout");
+    fill_chain_kernel_args(args.a, ph, dt);
+    fill_solve_args(args.a, io, prm);
+    if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
+    std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
+    args.T = T;
+    size_t nbytes = offsetof(Args, T) + sizeof(int);
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
+    return hipModuleLaunchKernel(prm.stop_sq_tol < 0.0 ? m.track_never : m.track_stop, static_cast<unsigned>((io.B + 63) / 64), 1, 1, 64, 1, 1, 0,
+                                 stream, nullptr, config);
 }
 
 // ---- the generic lane program specialised for ONE problem (device/generic_solver.hpp with IKD_STATIC_TABLES) -----------------------
@@ -892,6 +920,21 @@ hipError_t rtc_launch_chain_hot(const ProblemHost &ph, const DeviceTables &dt, c
     }
     switch (ph.chain.nj) {
 #define X(N) case N: return launch_shape<N>(ph, dt, io, prm, stream, m);
+        X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+#undef X
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t rtc_launch_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
+                                      hipStream_t stream) {
+    HotModule m;
+    {
+        hipError_t e = hipSuccess;
+        if (!module_for(ph, m, &e)) return e;
+    }
+    switch (ph.chain.nj) {
+#define X(N) case N: return launch_track_shape<N>(ph, dt, io, T, prm, stream, m);
         X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 #undef X
         default: return hipErrorInvalidValue;

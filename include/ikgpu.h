@@ -211,6 +211,29 @@ int ikgpu_dls_solve_batch(const ikgpu_problem *p, int64_t B, const double *q0, c
                           const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
                           int layout /* ikgpu_layout */, void *stream);
 
+/* ---- tracking: a SEQUENCE of T targets per problem, every waypoint started from the result of the one before.  Stands in for the
+ * reference caller's own loop (ik_ros/src/cassie.cpp:92-113: the target moves a little on every tick and q_ = ik::dls(*ik_, q_, ...)
+ * takes the previous result as the new start), B of them side by side.  DEFINED as T calls of ikgpu_dls_solve_batch on `stream`
+ * with the same params,
+ *   call k (k = 0 .. T-1):  q0 = (k == 0 ? q0 : slab k-1 of q_traj), targets = slab k of targets,
+ *                           q_out = slab k of q_traj, success = slab k of success, iters = slab k of iters
+ * and its outputs are bit-identical to what those calls write.  Waypoints are outermost:
+ *   q0      [nq x B]                 the start of waypoint 0
+ *   targets [T][ntasks x 12 x B]     q_traj [T][nq x B]     success [T][B] (may be NULL)     iters [T][B] (may be NULL)
+ * each slab in the batch layout (IKGPU_SOA / IKGPU_AOS) the single solve takes.  DEVICE pointers; asynchronous on `stream`.
+ * T == 0 or B == 0 is a no-op; T < 0 is IKGPU_ERR_INVALID.  A chain problem (`dls_chain<...>`) under the reference's visitor runs the
+ * whole sequence in ONE launch that keeps q in registers between waypoints (no queue slot, no allocation: capturable in a graph);
+ * every other problem kind and the derived visitors run the T launches from inside the call (when one fails, ikgpu_last_error()
+ * names the waypoint). */
+int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *targets,
+                          const ikgpu_dls_params *params, double *q_traj, uint8_t *success, int32_t *iters,
+                          int layout /* ikgpu_layout */, void *stream);
+/* Name of what ikgpu_dls_track_batch runs with these parameters: `dls_chain_track<NJ=7,full,hot>` (or hot-rtc / general: the build
+ * ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the chained launches.  The string
+ * belongs to the calling thread and lasts until its next call.  (The reference has one solver and no such choice: this names the
+ * stand-in of the caller's loop, ik_ros/src/cassie.cpp:92-113.) */
+const char *ikgpu_dls_track_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
+
 /* FrameTask::target (an SE(3), reference ik/ik/frame.hpp:189) given as 7 doubles -- translation (x y z), quaternion (qx qy qz qw;
  * converted as Eigen's toRotationMatrix does, i.e. as the free-flyer's configuration is read) -- expanded into the 12-double slots
  * the solve entry points take.  pose7: [ntasks x 7 x B] (IKGPU_SOA) or [B x ntasks x 7] (IKGPU_AOS); targets12 likewise with 12.
