@@ -618,6 +618,99 @@ def dls_track_batch(problem, Q0, targets, data, visitor=None, p=None, layout="so
     return Q, ok, it
 
 
+def dls_multistart_kernel(data, visitor=None, p=None, num_starts=8):
+    """Name of what dls_multistart_batch runs for these parameters: "dls_chain_multistart<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_multistart_kernel(data._h, C.byref(prm), num_starts).decode()
+
+
+def _check_starts(num_starts):
+    if not isinstance(num_starts, int) or not 1 <= num_starts <= 64:
+        raise ValueError("num_starts must be an integer in 1 .. 64, got %r" % (num_starts,))
+
+
+def multistart_starts(data, Q0, num_starts, seed=0, layout="soa"):
+    """The generated starts 1 .. num_starts-1 of dls_multistart_batch for (seed, Q0): [num_starts-1, nq, B] ("soa") or
+    [num_starts-1, B, nq] ("aos").  An entry is drawn uniformly between its limits when it lies in the task support, belongs to a revolute
+    or prismatic joint and both limits are finite; every other entry is Q0's.  A function of (seed, problem index, start index, entry)
+    only (include/ikgpu.h ikgpu_multistart_starts)."""
+    import torch
+    _check_starts(num_starts)
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    if len(Q0.shape) != 2:
+        raise ValueError("Q0 has shape %s, expected 2 dimensions" % (tuple(Q0.shape),))
+    if not (isinstance(Q0, torch.Tensor) and Q0.is_cuda and Q0.dtype == torch.float64):
+        raise TypeError("multistart_starts needs a float64 CUDA tensor")
+    if not Q0.is_contiguous():
+        raise ValueError("multistart_starts needs a contiguous tensor")
+    if Q0.device.index != data._device:
+        raise ValueError("Q0 lives on cuda:%s but the problem was created on device %d" % (Q0.device.index, data._device))
+    nq = len(data.support)
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    if tuple(Q0.shape) != ((nq, B) if lay == capi.SOA else (B, nq)):
+        raise ValueError("Q0 has shape %s, the problem has nq = %d" % (tuple(Q0.shape), nq))
+    out = torch.empty((num_starts - 1,) + tuple(Q0.shape), dtype=torch.float64, device=Q0.device)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream
+    capi.check(capi.lib().ikgpu_multistart_starts(data._h, B, num_starts, Q0.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), lay, C.c_void_p(s)))
+    return out
+
+
+def dls_multistart_batch(problem, Q0, targets, data, visitor=None, p=None, num_starts=8, seed=0, starts=None, layout="soa", out=None, stream=None):
+    """The best of num_starts solves per problem (ik::dls is a local method: reference ik/ik/dls.cpp:10, :73; the random_restart flag of
+    ik/ik/dls.hpp:27 stays inert).  Start 0 is Q0; starts 1 .. num_starts-1 are `starts` ([num_starts-1, nq, B] | [num_starts-1, B, nq])
+    or, when None, generated from `seed` (multistart_starts).  The winner is the lowest-index start that met the stop rule, else the one
+    with the smallest squared weighted error; Q / success / iterations are bit-identical to dls_batch from that start.  A chain problem
+    with num_starts in {2, 4, ..., 64} runs one launch with the starts of a problem in neighbouring lanes.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], targets [ntasks, 12, B]   |   "aos": Q0 [B, nq], targets [B, ntasks, 12]
+    out: (Q, success uint8 [B], iterations int32 [B], winner int32 [B], err_sq float64 [B]) preallocated, or None.
+    Returns (Q, success, iterations, winner, err_sq)."""
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    _check_starts(num_starts)
+    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
+    if len(Q0.shape) != 2 or len(targets.shape) != 3:
+        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(targets.shape)))
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
+    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
+        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
+    tensors = [Q0, targets] + ([starts] if starts is not None else [])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
+        raise TypeError("dls_multistart_batch needs float64 CUDA tensors")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError("dls_multistart_batch needs contiguous tensors")
+    if any(t.device.index != data._device for t in tensors):
+        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
+    if out is None:
+        Q = torch.empty_like(Q0)
+        ok = torch.empty((B,), dtype=torch.uint8, device=Q0.device)
+        it = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        win = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        err = torch.empty((B,), dtype=torch.float64, device=Q0.device)
+    else:
+        Q, ok, it, win, err = out
+        _check_tensor("out[0] (Q)", Q, tuple(Q0.shape), torch.float64, data._device)
+        _check_tensor("out[1] (success)", ok, (B,), torch.uint8, data._device)
+        _check_tensor("out[2] (iterations)", it, (B,), torch.int32, data._device)
+        _check_tensor("out[3] (winner)", win, (B,), torch.int32, data._device)
+        _check_tensor("out[4] (err_sq)", err, (B,), torch.float64, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_multistart_workspace_bytes(data._h, B, num_starts, C.byref(prm))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_multistart_batch(data._h, B, num_starts, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
+                                            seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
+                                            win.data_ptr(), err.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    return Q, ok, it, win, err
+
+
 def _check_tensor(name, t, shape, dtype, device):
     """A device buffer handed to the C ABI as a raw pointer: wrong dtype / device / stride / size would make the kernel read or
     write out of bounds, so it is refused here."""

@@ -85,6 +85,7 @@ struct ikgpu_problem {
     mutable uint64_t pik_static_key[2] = {0, 0};
     mutable bool pik_static[2] = {false, false};
     mutable std::string pik_static_name;
+    std::vector<uint8_t> draw;   // [nq] entries a generated start of a multi-start solve draws (problem.hpp multistart_draw_mask)
     std::string dls_name;    // what ikgpu_problem_kernel reports
     std::string pik_name;    // name of the generic PIK kernel instance
     std::string pik_tree_name;  // ... and of the tree kernel running a two-level ik::pik (when the problem has that shape)
@@ -410,6 +411,7 @@ int host_solve(const ikgpu_problem *p, int64_t B, const double *q0, const double
 
 namespace {
 int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_dls_params *params, hipStream_t st);
+int dispatch_eval(const ikgpu_problem *p, int64_t B, const double *q, const double *targets, double *e_out, double *J_out, int layout, hipStream_t st);
 }
 
 extern "C" {
@@ -557,6 +559,8 @@ int ikgpu_problem_create_constrained(const ikgpu_model *h, const ikgpu_task *tas
         up(&p->dev.lower, p->host.lower.data(), nq * sizeof(double));
         up(&p->dev.upper, p->host.upper.data(), nq * sizeof(double));
         up(&p->dev.q_in_chain, p->host.q_in_chain.data(), nq);
+        p->draw = ikgpu::multistart_draw_mask(h->m, p->host);
+        up(&p->dev.draw, p->draw.data(), nq);
         up(&p->dev.g_ints, p->gen.generic.ints.data(), p->gen.generic.ints.size() * sizeof(int32_t));
         up(&p->dev.g_dbls, p->gen.generic.dbls.data(), p->gen.generic.dbls.size() * sizeof(double));
         if (err == hipSuccess) err = p->dev.queues.grow();
@@ -644,6 +648,7 @@ void ikgpu_problem_destroy(ikgpu_problem *p) {
     (void)hipFree(p->dev.lower);
     (void)hipFree(p->dev.upper);
     (void)hipFree(p->dev.q_in_chain);
+    (void)hipFree(p->dev.draw);
     (void)hipFree(p->dev.chain_desc);
     (void)hipFree(p->dev.g_ints);
     (void)hipFree(p->dev.g_dbls);
@@ -715,9 +720,48 @@ int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_d
     return static_cast<int>(IKGPU_OK);
 }
 
+// The kernel dispatch of ikgpu_evaluate_batch for validated arguments, on the problem's device, inside `guarded`.
+int dispatch_eval(const ikgpu_problem *p, int64_t B, const double *q, const double *targets, double *e_out, double *J_out, int layout, hipStream_t st) {
+    hipError_t e = p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_eval_chain(p->host, p->dev, B, q, targets, e_out, J_out, layout, st)
+                   // (a tree problem with the demo's extras -- base-relative reference, alignment row -- has its stages evaluated
+                   // by the generic program: the tree stage kernel does not know them)
+                   : p->host.kind == ikgpu::KernelKind::Tree && !p->host.tree_extras()
+                       ? ikgpu::launch_eval_tree(p->host, p->dev, B, q, targets, e_out, J_out, nullptr, layout, st)
+                       : ikgpu::launch_eval_generic(p->gen, p->dev, B, q, targets, e_out, J_out, nullptr, layout, st);
+    if (e != hipSuccess) return hip_fail(e, "launching the evaluate kernel");
+    return static_cast<int>(IKGPU_OK);
+}
+
 // A chain problem under the reference's own visitor has a tracking kernel: one launch for the whole sequence.
 bool track_is_fused(const ikgpu_problem *p, const ikgpu_dls_params *params) {
     return p->host.kind == ikgpu::KernelKind::Chain && !p->dls_on_static_gen && !ikgpu::visitor_extended(*params);
+}
+
+// ... and a multi-start kernel when the K starts of a problem are a power-of-two group of lanes of one wave: log2 K, else -1.
+int multistart_fused_log2(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
+    if (!track_is_fused(p, params) || K < 2 || K > 64 || (K & (K - 1)) != 0) return -1;
+    int l = 0;
+    while ((1 << l) < K) ++l;
+    return l;
+}
+
+// The workspace of the multi-start definition run as a loop, carved in this order (each part rounded up to 256 bytes):
+// generated start [nq x B], q of the start's solve [nq x B], its error [M x B], best key [B], its iterations [B], its success flag [B].
+struct MultistartWorkspace {
+    size_t start, q, e, key, iters, success, total;
+};
+MultistartWorkspace multistart_workspace(const ikgpu_problem *p, int64_t B) {
+    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+    const size_t b = static_cast<size_t>(B), nq = static_cast<size_t>(p->host.nq), M = static_cast<size_t>(p->host.rows);
+    MultistartWorkspace w{};
+    w.start = 0;
+    w.q = w.start + up(8 * nq * b);
+    w.e = w.q + up(8 * nq * b);
+    w.key = w.e + up(8 * M * b);
+    w.iters = w.key + up(8 * b);
+    w.success = w.iters + up(4 * b);
+    w.total = w.success + up(b);
+    return w;
 }
 
 }  // namespace
@@ -767,6 +811,95 @@ int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const do
                 g_last_error = "waypoint " + std::to_string(k) + ": " + g_last_error;
                 return rc;
             }
+        }
+        return static_cast<int>(IKGPU_OK);
+    });
+}
+
+const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    if (multistart_fused_log2(p, params, K) >= 0) {   // "dls_chain<NJ=7,full,hot>" -> "dls_chain_multistart<NJ=7,full,hot>"
+        const size_t lt = p->dls_name.find('<');
+        name = p->dls_name.substr(0, lt) + "_multistart" + (lt == std::string::npos ? "" : p->dls_name.substr(lt));
+    } else {
+        name = "loop(" + p->dls_name + ")";
+    }
+    return name.c_str();
+}
+
+size_t ikgpu_dls_multistart_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, const ikgpu_dls_params *params) {
+    if (!p || !params || B <= 0 || K < 1 || K > 64 || multistart_fused_log2(p, params, K) >= 0) return 0;
+    return multistart_workspace(p, B).total;
+}
+
+int ikgpu_multistart_starts(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, uint64_t seed, double *starts_out, int layout,
+                            void *stream) {
+    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
+    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (K < 1 || K > 64) return fail(IKGPU_ERR_INVALID, "the number of starts must be 1 .. 64");
+    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (B == 0 || K == 1) return IKGPU_OK;   // start 0 is q0 itself: nothing to write
+    if (!q0 || !starts_out) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (B > (int64_t(1) << 31) * 32 / K) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
+    return guarded([&] {
+        DeviceGuard g(p->device);
+        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
+        const hipError_t e = ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, 1, K, q0, seed, starts_out, layout, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return hip_fail(e, "launching the multi-start draw");
+        return static_cast<int>(IKGPU_OK);
+    });
+}
+
+int ikgpu_dls_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, const double *starts, uint64_t seed,
+                               const double *targets, const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
+                               int32_t *winner, double *err_sq, int layout, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
+    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (K < 1 || K > 64) return fail(IKGPU_ERR_INVALID, "the number of starts must be 1 .. 64");
+    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_params(params)) return rc;
+    if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
+    if (!q0 || !targets || !q_out) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (B > (int64_t(1) << 31) * 32 / K) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
+    return guarded([&] {
+        DeviceGuard g(p->device);
+        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        const int log2K = multistart_fused_log2(p, params, K);
+        if (log2K >= 0) {
+            const ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
+            const ikdev::MultistartArgs ms{starts, p->dev.draw, seed, winner, err_sq, log2K};
+            const hipError_t e = ikgpu::launch_dls_chain_multistart(p->host, p->dev, io, ms, *params, st);
+            if (e != hipSuccess) return hip_fail(e, "launching the multi-start DLS kernel");
+            return static_cast<int>(IKGPU_OK);
+        }
+        // every other case: the definition itself, start after start on the same stream, merged into the caller's outputs
+        const MultistartWorkspace w = multistart_workspace(p, B);
+        if (!workspace || workspace_bytes < w.total)
+            return fail(IKGPU_ERR_INVALID, "multi-start workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                               std::to_string(w.total) + " needed (ikgpu_dls_multistart_workspace_bytes)");
+        char *ws = static_cast<char *>(workspace);
+        double *start = reinterpret_cast<double *>(ws + w.start), *q = reinterpret_cast<double *>(ws + w.q), *e = reinterpret_cast<double *>(ws + w.e);
+        unsigned long long *key = reinterpret_cast<unsigned long long *>(ws + w.key);
+        int32_t *it = reinterpret_cast<int32_t *>(ws + w.iters);
+        uint8_t *ok = reinterpret_cast<uint8_t *>(ws + w.success);
+        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B;
+        for (int k = 0; k < K; ++k) {
+            auto named = [&](int rc) {
+                g_last_error = "start " + std::to_string(k) + ": " + g_last_error;
+                return rc;
+            };
+            const double *from = k == 0 ? q0 : starts ? starts + (k - 1) * q_slab : start;
+            if (k > 0 && !starts) {
+                const hipError_t ed = ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, k, k + 1, q0, seed, start, layout, st);
+                if (ed != hipSuccess) return named(hip_fail(ed, "launching the multi-start draw"));
+            }
+            if (const int rc = dispatch_dls(p, ikgpu::BatchIO{B, from, targets, q, ok, it, layout}, params, st)) return named(rc);
+            if (const int rc = dispatch_eval(p, B, q, targets, e, nullptr, layout, st)) return named(rc);
+            const ikgpu::MultistartMerge m{B, p->host.nq, p->host.rows, layout, k, q, e, ok, it, key, q_out, success, iters, winner, err_sq};
+            const hipError_t em = ikgpu::launch_multistart_merge(m, st);
+            if (em != hipSuccess) return named(hip_fail(em, "launching the multi-start merge"));
         }
         return static_cast<int>(IKGPU_OK);
     });
@@ -884,15 +1017,7 @@ int ikgpu_evaluate_batch(const ikgpu_problem *p, int64_t B, const double *q, con
     return guarded([&] {
         DeviceGuard g(p->device);
         if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const hipStream_t st = static_cast<hipStream_t>(stream);
-        hipError_t e = p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_eval_chain(p->host, p->dev, B, q, targets, e_out, J_out, layout, st)
-                       // (a tree problem with the demo's extras -- base-relative reference, alignment row -- has its stages evaluated
-                       // by the generic program: the tree stage kernel does not know them)
-                       : p->host.kind == ikgpu::KernelKind::Tree && !p->host.tree_extras()
-                           ? ikgpu::launch_eval_tree(p->host, p->dev, B, q, targets, e_out, J_out, nullptr, layout, st)
-                           : ikgpu::launch_eval_generic(p->gen, p->dev, B, q, targets, e_out, J_out, nullptr, layout, st);
-        if (e != hipSuccess) return hip_fail(e, "launching the evaluate kernel");
-        return static_cast<int>(IKGPU_OK);
+        return dispatch_eval(p, B, q, targets, e_out, J_out, layout, static_cast<hipStream_t>(stream));
     });
 }
 

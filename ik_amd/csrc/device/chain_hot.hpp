@@ -298,7 +298,7 @@ IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const 
 // every load of a group issued before its first store: one entry per pass (load, wait, store; the next load cannot move above a
 // store that might alias it) cost one HBM round trip per entry -- nine for a Cassie leg, ~10 us of a 150 us launch.
 template <int NJ>
-IKD_FN void hot_pass_through_to(const ChainKernelArgs<NJ> &a, double *q_out, int64_t b, bool stepped) {
+IKD_FN void hot_pass_through_from(const ChainKernelArgs<NJ> &a, const double *q_src, double *q_out, int64_t b, bool stepped) {
     constexpr int kGroup = 16;   // (a Cassie model's sixteen entries in ONE pass: with groups of eight the second group's loads waited
                                  // for the first group's stores -- a second HBM round trip in the prologue)
     for (int i0 = 0; i0 < a.nq; i0 += kGroup) {
@@ -308,7 +308,7 @@ IKD_FN void hot_pass_through_to(const ChainKernelArgs<NJ> &a, double *q_out, int
         for (int k = 0; k < kGroup; ++k) {
             const int i = i0 + k < a.nq ? i0 + k : a.nq - 1;
             out[k] = i0 + k < a.nq && !a.q_in_chain[i];
-            v[k] = a.q0[at(a.layout, a.B, a.nq, i, b)];
+            v[k] = q_src[at(a.layout, a.B, a.nq, i, b)];
             lo[k] = a.lower[i];
             hi[k] = a.upper[i];
         }
@@ -319,6 +319,8 @@ IKD_FN void hot_pass_through_to(const ChainKernelArgs<NJ> &a, double *q_out, int
         }
     }
 }
+template <int NJ>
+IKD_FN void hot_pass_through_to(const ChainKernelArgs<NJ> &a, double *q_out, int64_t b, bool stepped) { hot_pass_through_from(a, a.q0, q_out, b, stepped); }
 template <int NJ>
 IKD_FN void hot_pass_through(const ChainKernelArgs<NJ> &a, int64_t b, bool stepped) { hot_pass_through_to(a, a.q_out, b, stepped); }
 
@@ -438,6 +440,40 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
     }
 }
 
+// K starts per problem, the best one stored -- dls_chain_multistart_body (chain_kernel_body.hpp: the definition, the lane mapping, the
+// three pieces) with the hot program: the unchanged hot_dls, then one more hot_evaluate at its result for the error alone (its Jacobian
+// columns are dead code).
+template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
+IKD_FN void hot_multistart_lane(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, const Tab &t, int64_t b, int k, double (&q)[NJ],
+                                bool &success, int &iters, double &err_sq, AnyFn any_active) {
+    multistart_load(a, ms, b, k, q);
+    double oMt[12];
+    load_target(a, b, oMt);
+    hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);
+    double e[6], col[NJ][6];
+    hot_evaluate<NJ, S>(t, q, oMt, e, col);
+    err_sq = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) err_sq = dfma(e[r], e[r], err_sq);
+}
+
+template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn, class Exchange>
+IKD_FN void hot_multistart_body(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, const Tab &t, int64_t gid, AnyFn any_active,
+                                Exchange exchange) {
+    const int64_t prob = gid >> ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq;
+    bool success;
+    int iters;
+    hot_multistart_lane<NJ, S, NEVERSTOP>(a, ms, t, b, k, q, success, iters, err_sq, any_active);
+    const int win = multistart_select(ms.log2K, multistart_key(success, err_sq), k, exchange);
+    if (valid && win == k)
+        multistart_store(a, ms, b, k, q, success, iters, err_sq,
+                         [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
+}
+
 #if IKD_HIP_LANG
 // ---- kernel entries, shared by the instantiations compiled into the library (kernels_hot.hip) and the ones compiled at run time for
 // a chain's own structure code (rtc.cpp) -----------------------------------------------------------------------------------------
@@ -476,6 +512,14 @@ __device__ __forceinline__ void hot_track_entry(const ChainKernelArgs<NJ> &a, co
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
     hot_track_body<NJ, S, NEVERSTOP>(a, tv, T, gid, KeepGoing{0, 0, 0});
+}
+
+template <int NJ, class S, bool NEVERSTOP>
+__device__ __forceinline__ void hot_multistart_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const MultistartArgs &ms) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    HotTable tv;
+    hot_park_table<NJ, S>(t, tv);
+    hot_multistart_body<NJ, S, NEVERSTOP>(a, ms, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
 }
 
 template <int NJ, class S>

@@ -7,6 +7,7 @@
 #endif
 
 #include "chain_solver.hpp"
+#include "multistart.hpp"
 
 namespace ikdev {
 
@@ -178,6 +179,90 @@ IKD_FN void dls_chain_track_body(const ChainKernelArgs<NJ> &a, const Desc &d, in
         }
         if (k + 2 < T) load_target_raw(a, a.targets + (k + 2) * t_slab, b, next);
     }
+}
+
+// ---- multi-start: K starts per problem in one launch, the best one stored (include/ikgpu.h ikgpu_dls_multistart_batch) ----------------
+// Defined through K calls of the single solve from K starts (start 0: the caller's q0; start k >= 1: slab k - 1 of the caller's
+// `starts`, or drawn from the seed -- device/multistart.hpp) and the error ikgpu_evaluate_batch defines at each result; ik::dls is a
+// local method (reference ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27).  Lane gid serves problem gid >> log2K with start gid & (K - 1): the
+// K starts of a problem are neighbouring lanes of one wave.  Three pieces, so that the CPU lane emulator can run them lane after lane:
+// the lane's own solve (below, and hot_multistart_lane), the selection (multistart_select) and the winner's stores (multistart_store).
+
+// Where start k of a problem reads entry i from: q0 (start 0, and the entries a generated start does not draw) or the caller's slab.
+template <int NJ>
+IKD_FN const double *multistart_source(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, int k) {
+    return (k == 0 || !ms.starts) ? a.q0 : ms.starts + static_cast<int64_t>(k - 1) * a.nq * a.B;
+}
+
+// The chain entries of start k of problem b.
+template <int NJ>
+IKD_FN void multistart_load(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, int64_t b, int k, double (&q)[NJ]) {
+    const double *src = multistart_source(a, ms, k);
+    const bool generated = k > 0 && !ms.starts;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int i = a.qidx[j];
+        const double v = src[at(a.layout, a.B, a.nq, i, b)];
+        const double r = multistart_draw(ms.seed, b, k, i, a.lower[i], a.upper[i]);
+        q[j] = (generated && ms.draw[i]) ? r : v;
+    }
+}
+
+// One start: the single solve's loop, unchanged, then one more evaluation at its result for the error alone.
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN void dls_chain_multistart_lane(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, const Desc &d, int64_t b, int k,
+                                      double (&q)[NJ], bool &success, int &iters, double &err_sq, AnyFn any_active) {
+    constexpr int M = TaskDim<KT>::value;
+    multistart_load(a, ms, b, k, q);
+    double oMt[12];
+    load_target(a, b, oMt);
+    chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active);
+    double e[M], col[NJ][M], Rf[9], pf[3];
+    chain_evaluate<NJ, KT, SMASK>(d, q, oMt, a.prm.idmask, a.prm.unit_weights != 0, e, col, Rf, pf);
+    err_sq = 0.0;
+#pragma unroll
+    for (int r = 0; r < M; ++r) err_sq = dfma(e[r], e[r], err_sq);
+}
+
+// The winning lane's stores: what the single solve from start k writes, over all nq entries, and the two outputs of the selection.
+// pass(src, stepped) writes the entries outside the chain from the start's own column.
+template <int NJ, class Pass>
+IKD_FN void multistart_store(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, int64_t b, int k, const double (&q)[NJ], bool success,
+                             int iters, double err_sq, Pass pass) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) a.q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+    pass(multistart_source(a, ms, k), iters > 0);
+    if (a.success) a.success[b] = success ? 1 : 0;
+    if (a.iters) a.iters[b] = iters;
+    if (ms.winner) ms.winner[b] = k;
+    if (ms.err_sq) ms.err_sq[b] = err_sq;
+}
+
+// Entries outside the task support of a solve started from column b of `src`: clipped once a step was taken (dls_chain_body).
+template <int NJ>
+IKD_FN void chain_pass_through_from(const ChainKernelArgs<NJ> &a, const double *src, int64_t b, bool stepped) {
+    for (int i = 0; i < a.nq; ++i) {
+        if (a.q_in_chain[i]) continue;
+        const double v = src[at(a.layout, a.B, a.nq, i, b)];
+        const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
+        a.q_out[at(a.layout, a.B, a.nq, i, b)] = stepped ? c : v;
+    }
+}
+
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn, class Exchange>
+IKD_FN void dls_chain_multistart_body(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, const Desc &d, int64_t gid, AnyFn any_active,
+                                      Exchange exchange) {
+    const int64_t prob = gid >> ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq;
+    bool success;
+    int iters;
+    dls_chain_multistart_lane<NJ, KT, SMASK>(a, ms, d, b, k, q, success, iters, err_sq, any_active);
+    const int win = multistart_select(ms.log2K, multistart_key(success, err_sq), k, exchange);
+    if (valid && win == k)
+        multistart_store(a, ms, b, k, q, success, iters, err_sq, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
 }
 
 #if IKD_HIP_LANG

@@ -703,6 +703,31 @@ inline void dls_track_device(InverseKinematicsProblem &problem, std::int64_t B, 
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// The best of K starts per problem on DEVICE buffers (ik::dls is a local method: ik/ik/dls.cpp:10 "try random walk", dls.cpp:73
+// "perform random restart"; dls_parameters::random_restart, ik/ik/dls.hpp:27, stays inert and ik::dls() is unchanged).  Start 0 is Q0,
+// starts 1 .. K-1 are `starts` [K-1][nq][B] or, when null, generated from `seed`; the winner is the lowest-index start that met the stop
+// rule, else the one with the smallest squared weighted error, and Q / success / iterations are bit-identical to dls_batch_device from
+// that start.  success / iterations / winner / err_sq [B] may be null.  workspace: device memory of multistart_workspace_bytes() bytes
+// (0 for a chain problem with K in {2, 4, .., 64}: one launch).  Asynchronous on `stream`.
+inline std::size_t multistart_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, int K, dls_data &data,
+                                              const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                              const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_multistart_workspace_bytes(data.handle(), B, K, &prm);
+}
+inline void dls_multistart_device(InverseKinematicsProblem &problem, std::int64_t B, int K, const number_t *Q0, const number_t *starts,
+                                  std::uint64_t seed, const number_t *targets, dls_data &data, number_t *Q, std::uint8_t *success,
+                                  std::int32_t *iterations, std::int32_t *winner, number_t *err_sq, void *workspace, std::size_t workspace_bytes,
+                                  void *stream, const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                  const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_multistart_batch(data.handle(), B, K, Q0, starts, seed, targets, &prm, Q, success, iterations, winner, err_sq, IKGPU_SOA, workspace,
+                                   workspace_bytes, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // ---- ik::pik, the prioritised solver (ik/ik/pik.hpp:11-59; ik/ik/pik.cpp:31-103) ---------------------
 struct pik_parameters {  // ik/ik/pik.hpp:11-16; the reference loop reads neither damping nor max_time
     int max_iterations = 100;

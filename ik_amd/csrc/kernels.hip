@@ -77,6 +77,53 @@ __global__ __launch_bounds__(kBlock) void dls_chain_track_kernel(const ChainKern
     ikdev::dls_chain_track_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, T, gid, ikdev::KeepGoing{0, 0, 0});
 }
 
+// K starts per problem in one launch, the best one stored (device/chain_kernel_body.hpp dls_chain_multistart_body): the general build's
+// multi-start kernel, with the SMASK build the single solve of the same problem takes, so that the bits are the same.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_multistart_kernel(const ChainKernelArgs<NJ> a, const ikdev::MultistartArgs ms) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    ikdev::dls_chain_multistart_body<NJ, KT, SMASK>(a, ms, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
+}
+
+struct MultistartStartsArgs {
+    const double *q0, *lower, *upper;
+    const uint8_t *draw;
+    double *out;
+    unsigned long long seed;
+    int64_t B;
+    int nq, layout, k0, k1;
+};
+__global__ __launch_bounds__(256) void multistart_starts_kernel(const MultistartStartsArgs a) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= a.B * (a.k1 - a.k0)) return;
+    const int64_t b = t % a.B;
+    const int s = static_cast<int>(t / a.B), k = a.k0 + s;
+    double *out = a.out + static_cast<int64_t>(s) * a.nq * a.B;
+    for (int i = 0; i < a.nq; ++i) {
+        const double v = a.q0[ikdev::at(a.layout, a.B, a.nq, i, b)];
+        out[ikdev::at(a.layout, a.B, a.nq, i, b)] = a.draw[i] ? ikdev::multistart_draw(a.seed, b, k, i, a.lower[i], a.upper[i]) : v;
+    }
+}
+
+__global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= m.B) return;
+    double err = 0.0;
+    for (int r = 0; r < m.M; ++r) {
+        const double e = m.e[ikdev::at(m.layout, m.B, m.M, r, b)];
+        err = ikdev::dfma(e, e, err);
+    }
+    const unsigned long long key = ikdev::multistart_key(m.success[b] != 0, err);
+    if (m.k > 0 && !(key < m.key[b])) return;   // (a tie keeps the lower index)
+    m.key[b] = key;
+    for (int i = 0; i < m.nq; ++i) m.q_out[ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
+    if (m.success_out) m.success_out[b] = m.success[b];
+    if (m.iters_out) m.iters_out[b] = m.iters[b];
+    if (m.winner) m.winner[b] = m.k;
+    if (m.err_sq) m.err_sq[b] = err;
+}
+
 struct PassThroughArgs {
     const double *q0, *lower, *upper;
     const uint8_t *q_in_chain;
@@ -168,6 +215,25 @@ hipError_t run_track(const ProblemHost &ph, const DeviceTables &dt, const BatchI
         }
     }
     hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, 0>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
+    return hipGetLastError();
+}
+
+template <int NJ, int KT>
+hipError_t run_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                          const ikgpu_dls_params &prm, hipStream_t stream) {
+    ChainKernelArgs<NJ> a = make_args<NJ>(ph, dt);
+    fill_solve_args(a, io, prm);
+    constexpr int kMask = HotMask<NJ>::value;   // the build run_dls picks for this problem
+    constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
+    const dim3 grid = grid_for(io.B << ms.log2K);
+    if constexpr (kMask != 0) {
+        if ((a.prm.idmask & kMask) == kMask) {
+            if (a.prm.unit_weights) hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, kHot>), grid, dim3(kBlock), 0, stream, a, ms);
+            else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, kMask>), grid, dim3(kBlock), 0, stream, a, ms);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, 0>), grid, dim3(kBlock), 0, stream, a, ms);
     return hipGetLastError();
 }
 
@@ -349,6 +415,35 @@ hipError_t launch_dls_chain_track(const ProblemHost &ph, const DeviceTables &dt,
     IKGPU_FOR_NJ(X)
 #undef X
     not_built(nj, type);
+}
+
+hipError_t launch_dls_chain_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                       const ikgpu_dls_params &prm, hipStream_t stream) {
+    if (ph.chain_build != 0) return launch_dls_chain_hot_multistart(ph, dt, io, ms, prm, stream);
+    const int nj = ph.chain.nj, type = ph.tasks[0].type;
+#define X(N)                                                                                                         \
+    if (nj == N) {                                                                                                   \
+        if (type == IKGPU_FULL) return run_multistart<N, ikdev::KT_FULL>(ph, dt, io, ms, prm, stream);               \
+        if (type == IKGPU_POSITION) return run_multistart<N, ikdev::KT_POSITION>(ph, dt, io, ms, prm, stream);       \
+        if (type == IKGPU_ORIENTATION) return run_multistart<N, ikdev::KT_ORIENTATION>(ph, dt, io, ms, prm, stream); \
+    }
+    IKGPU_FOR_NJ(X)
+#undef X
+    not_built(nj, type);
+}
+
+hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,
+                                    int layout, hipStream_t stream) {
+    if (k1 <= k0 || B <= 0) return hipSuccess;
+    const MultistartStartsArgs a{q0, dt.lower, dt.upper, dt.draw, out, seed, B, nq, layout, k0, k1};
+    const int64_t n = B * (k1 - k0);
+    hipLaunchKernelGGL(multistart_starts_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream) {
+    hipLaunchKernelGGL(multistart_merge, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
+    return hipGetLastError();
 }
 
 hipError_t launch_eval_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, const double *q,

@@ -8,6 +8,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device/multistart.hpp"
 #include "problem.hpp"
 
 namespace ikgpu {
@@ -38,6 +39,7 @@ struct QueuePool {
 struct DeviceTables {  // per-problem constant arrays resident in HBM
     double *lower = nullptr, *upper = nullptr;  // [nq]
     uint8_t *q_in_chain = nullptr;              // [nq]
+    uint8_t *draw = nullptr;                    // [nq] 1 where a generated start of a multi-start solve draws the entry (problem.hpp multistart_draw_mask)
     double *chain_desc = nullptr;               // ikdev::ChainDesc<NJ> / TreeDesc as a flat array of doubles
     int32_t *g_ints = nullptr;                  // generic kernel: packed int tables
     double *g_dbls = nullptr;                   // generic kernel: packed double tables
@@ -80,6 +82,33 @@ hipError_t launch_dls_chain_hot_track(const ProblemHost &ph, const DeviceTables 
                                       hipStream_t stream);
 hipError_t rtc_launch_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
                                       hipStream_t stream);
+// K = 1 << ms.log2K starts per problem in ONE launch, the best one stored (ikgpu_dls_multistart_batch; device/chain_kernel_body.hpp
+// dls_chain_multistart_body, device/chain_hot.hpp hot_multistart_body): B x K lanes, problem gid / K with start gid % K.  Chain problems
+// only, in the build the single solve takes; lock-step, no LDS, no queue slot, no allocation: capturable.
+hipError_t launch_dls_chain_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                       const ikgpu_dls_params &prm, hipStream_t stream);
+hipError_t launch_dls_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                           const ikgpu_dls_params &prm, hipStream_t stream);
+hipError_t rtc_launch_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                           const ikgpu_dls_params &prm, hipStream_t stream);
+// Starts k0 .. k1-1 (1 <= k0 <= k1) of every problem as ikgpu_multistart_starts defines them, start k into slab k - k0 of `out`.
+hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,
+                                    int layout, hipStream_t stream);
+// One step of the multi-start definition run as a loop: start k's single solve (q / success / iters) and its M-row error `e` against the
+// best so far in the caller's outputs; `key` [B] is the best rank so far (device/multistart.hpp multistart_key), k == 0 initialises.
+struct MultistartMerge {
+    int64_t B;
+    int nq, M, layout, k;
+    const double *q, *e;
+    const uint8_t *success;
+    const int32_t *iters;
+    unsigned long long *key;
+    double *q_out;
+    uint8_t *success_out;   // the four below: null or [B]
+    int32_t *iters_out, *winner;
+    double *err_sq;
+};
+hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream);
 bool chain_shape_built(int nj, int type);
 // The structure-specialised builds of the chain kernel (kernels_hot.hip, device/chain_hot.hpp): one Full task with unit
 // weights on a chain whose placement-structure code has an instantiation.  launch_dls_chain takes that route when it exists.

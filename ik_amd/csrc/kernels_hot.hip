@@ -47,6 +47,13 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_track_kernel(const Chain
     ikdev::hot_track_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, T);
 }
 
+// K starts per problem in one launch, the best one stored (device/chain_hot.hpp hot_multistart_body; include/ikgpu.h
+// ikgpu_dls_multistart_batch): lane gid serves problem gid / K with start gid % K.  Lock-step; no LDS, no queue slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_multistart_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::MultistartArgs ms) {
+    ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms);
+}
+
 // X(NJ, code0, code1, code2)
 #define IKGPU_HOT_SHAPES(X)                                                                                                   \
     X(7, 0x04f0208cce8c7664ull, 0x395959cacad65656ull, 0x000001cacace5656ull) /* Cassie leg: Left / RightFootFront, 22 values */ \
@@ -134,6 +141,29 @@ hipError_t launch_dls_chain_hot_track(const ProblemHost &ph, const DeviceTables 
         fill_solve_args(a, io, prm);                                                                                         \
         if (prm.stop_sq_tol < 0.0) hipLaunchKernelGGL((dls_chain_hot_track_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t, T); \
         else hipLaunchKernelGGL((dls_chain_hot_track_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t, T);  \
+        return hipGetLastError();                                                                                            \
+    }
+    IKGPU_HOT_SHAPES(X)
+#undef X
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_dls_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                           const ikgpu_dls_params &prm, hipStream_t stream) {
+    if (ph.chain_build == 2) return rtc_launch_chain_hot_multistart(ph, dt, io, ms, prm, stream);
+    const ChainStructure &s = ph.chain_struct;
+    const std::vector<double> &tab = ph.chain_hot;
+    HotTable t{};
+    if (tab.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
+    std::memcpy(t.v, tab.data(), tab.size() * sizeof(double));
+    const dim3 grid(static_cast<unsigned>(((io.B << ms.log2K) + kBlock - 1) / kBlock));
+#define X(N, K0, K1, K2)                                                                                                     \
+    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) {                                            \
+        ChainKernelArgs<N> a{};                                                                                              \
+        fill_chain_kernel_args(a, ph, dt);                                                                                   \
+        fill_solve_args(a, io, prm);                                                                                         \
+        if (prm.stop_sq_tol < 0.0) hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t, ms); \
+        else hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t, ms); \
         return hipGetLastError();                                                                                            \
     }
     IKGPU_HOT_SHAPES(X)

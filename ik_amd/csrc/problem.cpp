@@ -731,4 +731,16 @@ TreeArgsHost tree_args(const ProblemHost &ph) {
     return a;
 }
 
+std::vector<uint8_t> multistart_draw_mask(const Model &m, const ProblemHost &ph) {
+    std::vector<uint8_t> draw(static_cast<size_t>(m.nq), 0);
+    for (int32_t j = 0; j < m.njoints(); ++j) {
+        if (m.joint_type[j] != IKGPU_JOINT_REVOLUTE && m.joint_type[j] != IKGPU_JOINT_PRISMATIC) continue;
+        const size_t i = static_cast<size_t>(m.joint_idx_q[j]);
+        if (i >= draw.size() || i >= ph.q_in_chain.size() || !ph.q_in_chain[i]) continue;
+        const double lo = m.lower[i], hi = m.upper[i];
+        draw[i] = std::isfinite(lo) && std::isfinite(hi) && lo < hi ? 1 : 0;
+    }
+    return draw;
+}
+
 }  // namespace ikgpu

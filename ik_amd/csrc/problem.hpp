@@ -164,4 +164,9 @@ struct TreeArgsHost {
 };
 TreeArgsHost tree_args(const ProblemHost &ph);
 
+// Which entries of q a GENERATED start of a multi-start solve draws (include/ikgpu.h ikgpu_multistart_starts): in the task support, of a
+// revolute or prismatic joint, with finite limits lower < upper.  Every other entry -- the free-flyer's seven, an unbounded joint's --
+// keeps q0's value.  [nq], 1 = drawn.
+std::vector<uint8_t> multistart_draw_mask(const Model &m, const ProblemHost &ph);
+
 }  // namespace ikgpu

@@ -57,6 +57,7 @@
     extern "C" const char sym##_end[];
 IKGPU_EMBED(ikgpu_src_lane_math, "device/lane_math.hpp")
 IKGPU_EMBED(ikgpu_src_chain_solver, "device/chain_solver.hpp")
+IKGPU_EMBED(ikgpu_src_multistart, "device/multistart.hpp")
 IKGPU_EMBED(ikgpu_src_chain_kernel_body, "device/chain_kernel_body.hpp")
 IKGPU_EMBED(ikgpu_src_chain_hot, "device/chain_hot.hpp")
 IKGPU_EMBED(ikgpu_src_tree_solver, "device/tree_solver.hpp")
@@ -122,7 +123,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 // values: non-structural placement entries of the chain.  The refill kernel asks for two waves per SIMD (256 registers) unless the
 // parked table alone would take most of them.
 std::string hot_source(int nj, const uint64_t code[3], int values) {
-    char buf[4096];
+    char buf[6144];
     const char *refill_bounds = values <= 40 ? "__launch_bounds__(64, 2)" : "__launch_bounds__(64)";
     std::snprintf(buf, sizeof buf,
                   "#include \"chain_hot.hpp\"\n"
@@ -137,9 +138,14 @@ std::string hot_source(int nj, const uint64_t code[3], int values) {
                   "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_track_never(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const int T) {\n"
                   "    ikdev::hot_track_entry<%d, S, true>(a, t, T);\n}\n"
                   "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_track_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const int T) {\n"
-                  "    ikdev::hot_track_entry<%d, S, false>(a, t, T);\n}\n",
+                  "    ikdev::hot_track_entry<%d, S, false>(a, t, T);\n}\n"
+                  // K starts per problem in one launch, the best one stored (ikgpu_dls_multistart_batch)
+                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_multistart_never(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const ikdev::MultistartArgs ms) {\n"
+                  "    ikdev::hot_multistart_entry<%d, S, true>(a, t, ms);\n}\n"
+                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_multistart_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const ikdev::MultistartArgs ms) {\n"
+                  "    ikdev::hot_multistart_entry<%d, S, false>(a, t, ms);\n}\n",
                   static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]),
-                  nj, nj, nj, nj, refill_bounds, nj, nj, nj, nj, nj, nj);
+                  nj, nj, nj, nj, refill_bounds, nj, nj, nj, nj, nj, nj, nj, nj, nj, nj);
     return buf;
 }
 
@@ -222,7 +228,8 @@ struct HotCode {
 };
 struct HotModule {
     hipModule_t mod = nullptr;
-    hipFunction_t never = nullptr, stop = nullptr, refill = nullptr, track_never = nullptr, track_stop = nullptr;
+    hipFunction_t never = nullptr, stop = nullptr, refill = nullptr, track_never = nullptr, track_stop = nullptr, multistart_never = nullptr,
+                  multistart_stop = nullptr;
     int refill_waves_per_cu = 0;
 };
 
@@ -241,6 +248,7 @@ ShapeKey key_of(const ProblemHost &ph) {
 struct Hdr { const char *name, *begin, *end; };
 const Hdr kHeaders[] = {{"lane_math.hpp", ikgpu_src_lane_math, ikgpu_src_lane_math_end},
                         {"chain_solver.hpp", ikgpu_src_chain_solver, ikgpu_src_chain_solver_end},
+                        {"multistart.hpp", ikgpu_src_multistart, ikgpu_src_multistart_end},
                         {"chain_kernel_body.hpp", ikgpu_src_chain_kernel_body, ikgpu_src_chain_kernel_body_end},
                         {"chain_hot.hpp", ikgpu_src_chain_hot, ikgpu_src_chain_hot_end},
                         {"tree_solver.hpp", ikgpu_src_tree_solver, ikgpu_src_tree_solver_end},
@@ -491,6 +499,8 @@ bool module_for(const ProblemHost &ph, HotModule &out, hipError_t *err) {
         if (e == hipSuccess) e = hipModuleGetFunction(&m.refill, m.mod, "ikgpu_hot_refill");
         if (e == hipSuccess) e = hipModuleGetFunction(&m.track_never, m.mod, "ikgpu_hot_track_never");
         if (e == hipSuccess) e = hipModuleGetFunction(&m.track_stop, m.mod, "ikgpu_hot_track_stop");
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.multistart_never, m.mod, "ikgpu_hot_multistart_never");
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.multistart_stop, m.mod, "ikgpu_hot_multistart_stop");
         if (e == hipSuccess) {
             int per_cu = 0;
             if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.refill, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
@@ -563,6 +573,27 @@ hipError_t launch_track_shape(const ProblemHost &ph, const DeviceTables &dt, con
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
     return hipModuleLaunchKernel(prm.stop_sq_tol < 0.0 ? m.track_never : m.track_stop, static_cast<unsigned>((io.B + 63) / 64), 1, 1, 64, 1, 1, 0,
                                  stream, nullptr, config);
+}
+
+// The multi-start kernel of the same module: (ChainKernelArgs<NJ> a, HotTable t, MultistartArgs ms), one launch over B x K lanes.
+template <int NJ>
+hipError_t launch_multistart_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                   const ikgpu_dls_params &prm, hipStream_t stream, const HotModule &m) {
+    struct Args {
+        ikdev::ChainKernelArgs<NJ> a;
+        ikdev::HotTable t;
+        ikdev::MultistartArgs ms;
+    } args{};
+    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8, "argument layout");
+    fill_chain_kernel_args(args.a, ph, dt);
+    fill_solve_args(args.a, io, prm);
+    if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
+    std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
+    args.ms = ms;
+    size_t nbytes = sizeof(Args);
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
+    return hipModuleLaunchKernel(prm.stop_sq_tol < 0.0 ? m.multistart_never : m.multistart_stop,
+                                 static_cast<unsigned>(((io.B << ms.log2K) + 63) / 64), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
 }
 
 // ---- the generic lane program specialised for ONE problem (device/generic_solver.hpp with IKD_STATIC_TABLES) -----------------------
@@ -935,6 +966,21 @@ hipError_t rtc_launch_chain_hot_track(const ProblemHost &ph, const DeviceTables 
     }
     switch (ph.chain.nj) {
 #define X(N) case N: return launch_track_shape<N>(ph, dt, io, T, prm, stream, m);
+        X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+#undef X
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t rtc_launch_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
+                                           const ikgpu_dls_params &prm, hipStream_t stream) {
+    HotModule m;
+    {
+        hipError_t e = hipSuccess;
+        if (!module_for(ph, m, &e)) return e;
+    }
+    switch (ph.chain.nj) {
+#define X(N) case N: return launch_multistart_shape<N>(ph, dt, io, ms, prm, stream, m);
         X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 #undef X
         default: return hipErrorInvalidValue;

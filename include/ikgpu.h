@@ -234,6 +234,49 @@ int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const do
  * stand-in of the caller's loop, ik_ros/src/cassie.cpp:92-113.) */
 const char *ikgpu_dls_track_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
 
+/* ---- multi-start: the best of K starts per problem.  ik::dls is a local method and the reference says so itself (ik/ik/dls.cpp:10
+ * "todo - if limited convergence, try random walk"; dls.cpp:73 "If issues, perform random restart"; dls_parameters::random_restart,
+ * ik/ik/dls.hpp:27, is a flag nothing reads -- it stays inert here too).  1 <= K <= 64, else IKGPU_ERR_INVALID.  DEFINED through K calls
+ * of ikgpu_dls_solve_batch with the same targets and params:
+ *   start 0 of problem b is its column of q0; start k >= 1 is slab k-1 of `starts` ([K-1][nq x B], each slab in the batch layout)
+ *   when starts != NULL, else the generated start ikgpu_multistart_starts writes for (seed, b, k);
+ *   r_k = (q_k, success_k, iters_k) is what the single solve writes from start k, err_k the sum of squares, in row order, of the M-row
+ *   weighted error ikgpu_evaluate_batch defines at q_k;
+ *   the winner is the k with the smallest key (success_k ? 0 : 1, success_k ? 0 : err_k, k): among the starts that met the stop rule
+ *   the lowest index (the caller's own start wins when it converges: a warm start keeps its branch), otherwise the smallest error; a
+ *   non-finite err_k ranks as +infinity.  Under the never-stop visitor: the arg-min of the error.
+ * q_out [nq x B], success [B], iters [B] are r_winner bit for bit, over all nq entries; winner [B] is the start's index and err_sq [B] is
+ * err_winner.  success, iters, winner and err_sq may each be NULL.  DEVICE pointers; asynchronous on `stream`; B == 0 is a no-op.
+ * q_out must not overlap q0 or starts.
+ * A chain problem under the reference's visitor with K in {2, 4, 8, 16, 32, 64} runs ONE launch (`dls_chain_multistart<...>`): lane
+ * gid solves problem gid / K from start gid % K, the K lanes of a group compare their keys across lanes and the winner alone stores
+ * (no LDS, no queue slot, no allocation: capturable in a graph; `workspace` is not read).  Every other case -- tree, generic,
+ * static-program and derived-visitor problems, K = 1, K not a power of two -- runs the definition from inside the call, start after
+ * start, in `workspace` (DEVICE memory of at least ikgpu_dls_multistart_workspace_bytes bytes, else IKGPU_ERR_INVALID); when a step
+ * fails, ikgpu_last_error() names the start. */
+int ikgpu_dls_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, const double *starts, uint64_t seed,
+                               const double *targets, const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
+                               int32_t *winner, double *err_sq, int layout /* ikgpu_layout */, void *workspace, size_t workspace_bytes,
+                               void *stream);
+/* Bytes of `workspace` ikgpu_dls_multistart_batch needs for these arguments: 0 for the single launch.  (The restarts the reference
+ * only plans -- ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- need no memory there either: this serves the loop that stands in for them.) */
+size_t ikgpu_dls_multistart_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, const ikgpu_dls_params *params);
+/* The generated starts 1 .. K-1 (the random restart of reference ik/ik/dls.cpp:10, :73 and ik/ik/dls.hpp:27, made reproducible):
+ * starts_out [K-1][nq x B].  Entry i of a start is DRAWN only if ikgpu_problem_support says 1 for i, i belongs to a revolute or
+ * prismatic joint, and both limits are finite with lower[i] < upper[i]; every other entry (the free-flyer's seven, an unbounded
+ * joint's) is q0's, bit for bit.  The draw, in uint64 wrapping arithmetic:
+ *   mix(z): z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31
+ *   h = mix(seed + 0x9E3779B97F4A7C15); h = mix(h + b); h = mix(h + k); h = mix(h + i)
+ *   u = (h >> 11) * 2^-53;   value = clip(fma(u, upper[i] - lower[i], lower[i]), lower[i], upper[i])
+ * a function of (seed, b, k, i) only: not of B, K, the layout or the build.  K == 1 writes nothing. */
+int ikgpu_multistart_starts(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, uint64_t seed,
+                            double *starts_out /* [K-1][nq x B] */, int layout /* ikgpu_layout */, void *stream);
+/* Name of what ikgpu_dls_multistart_batch runs with these parameters and K: `dls_chain_multistart<NJ=7,full,hot>` (or hot-rtc /
+ * general: the build ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the definition run
+ * start after start.  The string belongs to the calling thread and lasts until its next call.  (The reference plans its restarts --
+ * ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- and has no such choice.) */
+const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K);
+
 /* FrameTask::target (an SE(3), reference ik/ik/frame.hpp:189) given as 7 doubles -- translation (x y z), quaternion (qx qy qz qw;
  * converted as Eigen's toRotationMatrix does, i.e. as the free-flyer's configuration is read) -- expanded into the 12-double slots
  * the solve entry points take.  pose7: [ntasks x 7 x B] (IKGPU_SOA) or [B x ntasks x 7] (IKGPU_AOS); targets12 likewise with 12.
