@@ -712,7 +712,7 @@ int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_d
         return static_cast<int>(IKGPU_OK);
     }
     hipError_t e = p->dls_on_static_gen                      ? ikgpu::rtc_launch_generic_static(p->gen, p->gen.generic_key, io, *params, st, p->dev.queues)
-                   : p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_dls_chain(p->host, p->dev, io, *params, st)
+                   : p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_dls_chain(p->host, p->dev, io, ikgpu::ChainJob{}, *params, st)
                    : p->host.kind == ikgpu::KernelKind::Tree ? ikgpu::launch_dls_tree(p->host, p->dev, io, *params, st)
                    : p->host.generic_build == 2              ? ikgpu::rtc_launch_generic_static(p->host, p->host.generic_key, io, *params, st, p->dev.queues)
                                                              : ikgpu::launch_dls_generic(p->host, p->dev, io, *params, st);
@@ -745,6 +745,14 @@ int multistart_fused_log2(const ikgpu_problem *p, const ikgpu_dls_params *params
     return l;
 }
 
+// What a tracking or multi-start call runs: the fused kernel, "dls_chain<NJ=7,full,hot>" -> "dls_chain_track<NJ=7,full,hot>" for the
+// suffix "_track", or the loop over the single solve.
+std::string variant_kernel_name(const ikgpu_problem *p, bool fused, const char *suffix) {
+    if (!fused) return "loop(" + p->dls_name + ")";
+    const size_t lt = p->dls_name.find('<');
+    return p->dls_name.substr(0, lt) + suffix + (lt == std::string::npos ? "" : p->dls_name.substr(lt));
+}
+
 // The workspace of the multi-start definition run as a loop, carved in this order (each part rounded up to 256 bytes):
 // generated start [nq x B], q of the start's solve [nq x B], its error [M x B], best key [B], its iterations [B], its success flag [B].
 struct MultistartWorkspace {
@@ -771,12 +779,7 @@ extern "C" {
 const char *ikgpu_dls_track_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params) {
     if (!p || !params) return "";
     thread_local std::string name;
-    if (track_is_fused(p, params)) {   // "dls_chain<NJ=7,full,hot>" -> "dls_chain_track<NJ=7,full,hot>"
-        const size_t lt = p->dls_name.find('<');
-        name = p->dls_name.substr(0, lt) + "_track" + (lt == std::string::npos ? "" : p->dls_name.substr(lt));
-    } else {
-        name = "loop(" + p->dls_name + ")";
-    }
+    name = variant_kernel_name(p, track_is_fused(p, params), "_track");
     return name.c_str();
 }
 
@@ -798,7 +801,8 @@ int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const do
         const hipStream_t st = static_cast<hipStream_t>(stream);
         if (track_is_fused(p, params)) {
             const ikgpu::BatchIO io{B, q0, targets, q_traj, success, iters, layout};
-            const hipError_t e = ikgpu::launch_dls_chain_track(p->host, p->dev, io, static_cast<int>(T), *params, st);
+            const ikgpu::ChainJob job{ikgpu::ChainJob::Track, static_cast<int>(T)};
+            const hipError_t e = ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st);
             if (e != hipSuccess) return hip_fail(e, "launching the DLS tracking kernel");
             return static_cast<int>(IKGPU_OK);
         }
@@ -819,12 +823,7 @@ int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const do
 const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
     if (!p || !params) return "";
     thread_local std::string name;
-    if (multistart_fused_log2(p, params, K) >= 0) {   // "dls_chain<NJ=7,full,hot>" -> "dls_chain_multistart<NJ=7,full,hot>"
-        const size_t lt = p->dls_name.find('<');
-        name = p->dls_name.substr(0, lt) + "_multistart" + (lt == std::string::npos ? "" : p->dls_name.substr(lt));
-    } else {
-        name = "loop(" + p->dls_name + ")";
-    }
+    name = variant_kernel_name(p, multistart_fused_log2(p, params, K) >= 0, "_multistart");
     return name.c_str();
 }
 
@@ -869,8 +868,8 @@ int ikgpu_dls_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, con
         const int log2K = multistart_fused_log2(p, params, K);
         if (log2K >= 0) {
             const ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
-            const ikdev::MultistartArgs ms{starts, p->dev.draw, seed, winner, err_sq, log2K};
-            const hipError_t e = ikgpu::launch_dls_chain_multistart(p->host, p->dev, io, ms, *params, st);
+            const ikgpu::ChainJob job{ikgpu::ChainJob::Multistart, 0, ikdev::MultistartArgs{starts, p->dev.draw, seed, winner, err_sq, log2K}};
+            const hipError_t e = ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st);
             if (e != hipSuccess) return hip_fail(e, "launching the multi-start DLS kernel");
             return static_cast<int>(IKGPU_OK);
         }

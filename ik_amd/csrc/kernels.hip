@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "device/chain_kernel_body.hpp"
 #include "device/pik_solver.hpp"
@@ -68,8 +69,7 @@ __global__ __launch_bounds__(kBlock) void dls_chain_refill_kernel(const ChainKer
     ikdev::dls_chain_refill_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, queue, chunk);
 }
 
-// T chained solves per problem in one launch (device/chain_kernel_body.hpp dls_chain_track_body): the general build's tracking kernel,
-// with the placement mask / weights build (SMASK) the single solve of the same problem takes, so that the bits are the same.
+// T chained solves per problem in one launch (device/chain_kernel_body.hpp dls_chain_track_body): the general build's tracking kernel.
 template <int NJ, int KT, int SMASK>
 __global__ __launch_bounds__(kBlock) void dls_chain_track_kernel(const ChainKernelArgs<NJ> a, const int T) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void dls_chain_track_kernel(const ChainKern
 }
 
 // K starts per problem in one launch, the best one stored (device/chain_kernel_body.hpp dls_chain_multistart_body): the general build's
-// multi-start kernel, with the SMASK build the single solve of the same problem takes, so that the bits are the same.
+// multi-start kernel.
 template <int NJ, int KT, int SMASK>
 __global__ __launch_bounds__(kBlock) void dls_chain_multistart_kernel(const ChainKernelArgs<NJ> a, const ikdev::MultistartArgs ms) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
@@ -181,60 +181,37 @@ hipError_t run_dls_build(const ProblemHost &ph, const DeviceTables &dt, const Ba
     });
 }
 
-template <int NJ, int KT>
-hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm,
-                   hipStream_t stream) {
-    ChainKernelArgs<NJ> a = make_args<NJ>(ph, dt);
-    fill_solve_args(a, io, prm);
-    // two builds per shape: the hot one (known placement mask + unit weights, all folded at compile time) and the
-    // general one (nothing skipped, weights always applied); neither has a branch inside the iteration
-    // ... and, for the shapes with a known mask, one in between: the mask folded, the weights applied (a weighted task on a
-    // Cassie leg or a UR arm keeps the skipped placement products)
+// The build of the general chain kernel a problem runs on, f(std::integral_constant<int, SMASK>).  Two builds per shape: the hot one
+// (known placement mask + unit weights, all folded at compile time) and the general one (nothing skipped, weights always applied);
+// neither has a branch inside the iteration ... and, for the shapes with a known mask, one in between: the mask folded, the weights
+// applied (a weighted task on a Cassie leg or a UR arm keeps the skipped placement products).  Every kind of job takes its kernel from
+// this one choice, which is what makes a tracking or multi-start launch return the single solve's bits.
+template <int NJ, class F>
+hipError_t with_chain_build(int idmask, bool unit_weights, F f) {
     constexpr int kMask = HotMask<NJ>::value;
     constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
     if constexpr (kMask != 0) {
-        if ((a.prm.idmask & kMask) == kMask) {
-            if (a.prm.unit_weights) return run_dls_build<NJ, KT, kHot>(ph, dt, io, prm, stream, a);
-            return run_dls_build<NJ, KT, kMask>(ph, dt, io, prm, stream, a);
+        if ((idmask & kMask) == kMask) {
+            if (unit_weights) return f(std::integral_constant<int, kHot>{});
+            return f(std::integral_constant<int, kMask>{});
         }
     }
-    return run_dls_build<NJ, KT, 0>(ph, dt, io, prm, stream, a);
+    return f(std::integral_constant<int, 0>{});
 }
 
 template <int NJ, int KT>
-hipError_t run_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm, hipStream_t stream) {
+hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
+                   hipStream_t stream) {
     ChainKernelArgs<NJ> a = make_args<NJ>(ph, dt);
     fill_solve_args(a, io, prm);
-    constexpr int kMask = HotMask<NJ>::value;   // the build run_dls picks for this problem
-    constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
-    if constexpr (kMask != 0) {
-        if ((a.prm.idmask & kMask) == kMask) {
-            if (a.prm.unit_weights) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, kHot>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
-            else hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, kMask>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, 0>), grid_for(io.B), dim3(kBlock), 0, stream, a, T);
-    return hipGetLastError();
-}
-
-template <int NJ, int KT>
-hipError_t run_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                          const ikgpu_dls_params &prm, hipStream_t stream) {
-    ChainKernelArgs<NJ> a = make_args<NJ>(ph, dt);
-    fill_solve_args(a, io, prm);
-    constexpr int kMask = HotMask<NJ>::value;   // the build run_dls picks for this problem
-    constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
-    const dim3 grid = grid_for(io.B << ms.log2K);
-    if constexpr (kMask != 0) {
-        if ((a.prm.idmask & kMask) == kMask) {
-            if (a.prm.unit_weights) hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, kHot>), grid, dim3(kBlock), 0, stream, a, ms);
-            else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, kMask>), grid, dim3(kBlock), 0, stream, a, ms);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, 0>), grid, dim3(kBlock), 0, stream, a, ms);
-    return hipGetLastError();
+    return with_chain_build<NJ>(a.prm.idmask, a.prm.unit_weights != 0, [&](auto smask) -> hipError_t {
+        constexpr int SM = decltype(smask)::value;
+        if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
+        const dim3 grid = grid_for(job.lanes(io.B));
+        if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
+        else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.ms);
+        return hipGetLastError();
+    });
 }
 
 template <int NJ, int KT>
@@ -387,45 +364,15 @@ bool chain_shape_built(int nj, int type) {
     return nj >= 1 && nj <= kMaxChain && (type == IKGPU_FULL || type == IKGPU_POSITION || type == IKGPU_ORIENTATION);
 }
 
-hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io,
+hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job,
                             const ikgpu_dls_params &prm, hipStream_t stream) {
-    if (ph.chain_build != 0) return launch_dls_chain_hot(ph, dt, io, prm, stream);   // structure-specialised build (kernels_hot.hip / rtc.cpp)
-    const int nj = ph.chain.nj, type = ph.tasks[0].type;
-#define X(N)                                                                                              \
-    if (nj == N) {                                                                                        \
-        if (type == IKGPU_FULL) return run_dls<N, ikdev::KT_FULL>(ph, dt, io, prm, stream);               \
-        if (type == IKGPU_POSITION) return run_dls<N, ikdev::KT_POSITION>(ph, dt, io, prm, stream);       \
-        if (type == IKGPU_ORIENTATION) return run_dls<N, ikdev::KT_ORIENTATION>(ph, dt, io, prm, stream); \
-    }
-    IKGPU_FOR_NJ(X)
-#undef X
-    not_built(nj, type);
-}
-
-hipError_t launch_dls_chain_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                                  hipStream_t stream) {
-    if (ph.chain_build != 0) return launch_dls_chain_hot_track(ph, dt, io, T, prm, stream);
+    if (ph.chain_build != 0) return launch_dls_chain_hot(ph, dt, io, job, prm, stream);   // structure-specialised build (kernels_hot.hip / rtc.cpp)
     const int nj = ph.chain.nj, type = ph.tasks[0].type;
 #define X(N)                                                                                                   \
     if (nj == N) {                                                                                             \
-        if (type == IKGPU_FULL) return run_track<N, ikdev::KT_FULL>(ph, dt, io, T, prm, stream);               \
-        if (type == IKGPU_POSITION) return run_track<N, ikdev::KT_POSITION>(ph, dt, io, T, prm, stream);       \
-        if (type == IKGPU_ORIENTATION) return run_track<N, ikdev::KT_ORIENTATION>(ph, dt, io, T, prm, stream); \
-    }
-    IKGPU_FOR_NJ(X)
-#undef X
-    not_built(nj, type);
-}
-
-hipError_t launch_dls_chain_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                       const ikgpu_dls_params &prm, hipStream_t stream) {
-    if (ph.chain_build != 0) return launch_dls_chain_hot_multistart(ph, dt, io, ms, prm, stream);
-    const int nj = ph.chain.nj, type = ph.tasks[0].type;
-#define X(N)                                                                                                         \
-    if (nj == N) {                                                                                                   \
-        if (type == IKGPU_FULL) return run_multistart<N, ikdev::KT_FULL>(ph, dt, io, ms, prm, stream);               \
-        if (type == IKGPU_POSITION) return run_multistart<N, ikdev::KT_POSITION>(ph, dt, io, ms, prm, stream);       \
-        if (type == IKGPU_ORIENTATION) return run_multistart<N, ikdev::KT_ORIENTATION>(ph, dt, io, ms, prm, stream); \
+        if (type == IKGPU_FULL) return run_dls<N, ikdev::KT_FULL>(ph, dt, io, job, prm, stream);               \
+        if (type == IKGPU_POSITION) return run_dls<N, ikdev::KT_POSITION>(ph, dt, io, job, prm, stream);       \
+        if (type == IKGPU_ORIENTATION) return run_dls<N, ikdev::KT_ORIENTATION>(ph, dt, io, job, prm, stream); \
     }
     IKGPU_FOR_NJ(X)
 #undef X

@@ -65,32 +65,29 @@ struct BatchIO {
     int layout;             // ikgpu_layout
 };
 
+// What a launch of the chain kernel is asked for, in the build the problem's single solve takes (general / hot / run-time compiled
+// hot), so that every kind returns the single solve's bits:
+//   Solve:      one solve per problem, in the stop-rule mode the batch asks for (run_stop_rule).
+//   Track:      T chained solves per problem in ONE launch, q on-chip between them (ikgpu_dls_track_batch; device/chain_kernel_body.hpp
+//               dls_chain_track_body, device/chain_hot.hpp hot_track_body): `io` holds the pointers of waypoint 0, waypoint k's slab of
+//               targets / q_out / success / iters follows at k times the slab's size.
+//   Multistart: K = 1 << ms.log2K starts per problem in ONE launch, the best one stored (ikgpu_dls_multistart_batch;
+//               dls_chain_multistart_body, hot_multistart_body): B x K lanes, problem gid / K with start gid % K.
+// Track and Multistart are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is capturable.
+struct ChainJob {
+    enum Kind { Solve, Track, Multistart } kind = Solve;
+    int T = 0;                     // Track: the number of waypoints
+    ikdev::MultistartArgs ms{};    // Multistart
+    int64_t lanes(int64_t B) const { return kind == Multistart ? B << ms.log2K : B; }   // one lane per problem, or per start
+};
+
 // Returns hipSuccess or the launch error. Throws std::runtime_error for an un-instantiated shape.
-hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io,
+hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job,
                             const ikgpu_dls_params &prm, hipStream_t stream);
 hipError_t launch_eval_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, const double *q, const double *targets,
                              double *e_out, double *J_out, int layout, hipStream_t stream);
 hipError_t launch_fk_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, const double *q, double *oMf_out, int layout,
                            hipStream_t stream);
-// T chained solves per problem in ONE launch, q on-chip between them (ikgpu_dls_track_batch; device/chain_kernel_body.hpp
-// dls_chain_track_body, device/chain_hot.hpp hot_track_body): `io` holds the pointers of waypoint 0, waypoint k's slab of targets /
-// q_out / success / iters follows at k times the slab's size.  Chain problems only, in the build the single solve takes (general /
-// hot / run-time compiled hot); always lock-step per waypoint, so the launch needs no queue slot and is capturable.
-hipError_t launch_dls_chain_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                                  hipStream_t stream);
-hipError_t launch_dls_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                                      hipStream_t stream);
-hipError_t rtc_launch_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                                      hipStream_t stream);
-// K = 1 << ms.log2K starts per problem in ONE launch, the best one stored (ikgpu_dls_multistart_batch; device/chain_kernel_body.hpp
-// dls_chain_multistart_body, device/chain_hot.hpp hot_multistart_body): B x K lanes, problem gid / K with start gid % K.  Chain problems
-// only, in the build the single solve takes; lock-step, no LDS, no queue slot, no allocation: capturable.
-hipError_t launch_dls_chain_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                       const ikgpu_dls_params &prm, hipStream_t stream);
-hipError_t launch_dls_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                           const ikgpu_dls_params &prm, hipStream_t stream);
-hipError_t rtc_launch_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                           const ikgpu_dls_params &prm, hipStream_t stream);
 // Starts k0 .. k1-1 (1 <= k0 <= k1) of every problem as ikgpu_multistart_starts defines them, start k into slab k - k0 of `out`.
 hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,
                                     int layout, hipStream_t stream);
@@ -253,11 +250,12 @@ bool rtc_generic_static_precompile_refill(const ProblemHost &gen);   // the refi
 bool rtc_pik_static_available(const ProblemHost &gen, bool with_da, bool compile, uint64_t *key_out);
 hipError_t rtc_launch_pik_static(const ProblemHost &gen, uint64_t key, const BatchIO &io, const ikgpu_pik_params &prm, hipStream_t stream);
 std::string rtc_last_log();   // compiler log (or cache note) of the calling process's last run-time compilation attempt
-hipError_t rtc_launch_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream);
+hipError_t rtc_launch_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
+                                hipStream_t stream);
 hipError_t launch_targets_from_pose7(int64_t B, int ntasks, const double *pose7, double *targets12, int layout, hipStream_t stream);
 int64_t persistent_grid(const void *kernel, int block, size_t lds, int64_t nblocks);
 bool raise_lds_limit(const void *kernel, size_t lds);
-hipError_t launch_dls_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm,
+hipError_t launch_dls_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
                                 hipStream_t stream);
 
 }  // namespace ikgpu

@@ -12,6 +12,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "device/chain_hot.hpp"
 
@@ -93,79 +94,51 @@ std::string chain_kernel_name(const ProblemHost &ph) {
     return n.substr(0, cut) + (ph.chain_build == 1 ? ",hot>" : ph.chain_build == 2 ? ",hot-rtc>" : ",general>");
 }
 
-hipError_t launch_dls_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm,
+namespace {
+
+// One pre-built shape: the kernel the job asks for, on the never-stop visitor's own instantiation when the call has no stop rule.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
+hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
+                            hipStream_t stream, const HotTable &t) {
+    ChainKernelArgs<NJ> a{};
+    fill_chain_kernel_args(a, ph, dt);
+    fill_solve_args(a, io, prm);
+    const dim3 grid(static_cast<unsigned>((job.lanes(io.B) + kBlock - 1) / kBlock)), block(kBlock);
+    auto launch = [&](auto never) -> hipError_t {
+        constexpr bool NEVER = decltype(never)::value;
+        if (job.kind == ChainJob::Track) {
+            hipLaunchKernelGGL((dls_chain_hot_track_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.T);
+        } else if (job.kind == ChainJob::Multistart) {
+            hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.ms);
+        } else if constexpr (NEVER) {
+            hipLaunchKernelGGL((dls_chain_hot_kernel<NJ, C0, C1, C2, true>), grid, block, 0, stream, a, t);
+        } else {
+            const int64_t rgrid = refill_grid(reinterpret_cast<const void *>(dls_chain_hot_refill_kernel<NJ, C0, C1, C2>), io.B);
+            return run_stop_rule(dt.queues, io, prm, stream, a, false, rgrid, PassThrough{&ph, &dt}, [&] {
+                hipLaunchKernelGGL((dls_chain_hot_kernel<NJ, C0, C1, C2, false>), grid, block, 0, stream, a, t);
+                return hipGetLastError();
+            }, [&](unsigned long long *queue, int chunk) {
+                hipLaunchKernelGGL((dls_chain_hot_refill_kernel<NJ, C0, C1, C2>), dim3(static_cast<unsigned>(rgrid)), block, 0, stream, a, t, queue, chunk);
+                return hipGetLastError();
+            });
+        }
+        return hipGetLastError();
+    };
+    return prm.stop_sq_tol < 0.0 ? launch(std::true_type{}) : launch(std::false_type{});
+}
+
+}  // namespace
+
+hipError_t launch_dls_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
                                 hipStream_t stream) {
-    if (ph.chain_build == 2) return rtc_launch_chain_hot(ph, dt, io, prm, stream);
+    if (ph.chain_build == 2) return rtc_launch_chain_hot(ph, dt, io, job, prm, stream);
     const ChainStructure &s = ph.chain_struct;
     const std::vector<double> &tab = ph.chain_hot;
     HotTable t{};
     if (tab.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
     std::memcpy(t.v, tab.data(), tab.size() * sizeof(double));
-    const dim3 grid(static_cast<unsigned>((io.B + kBlock - 1) / kBlock));
-#define X(N, K0, K1, K2)                                                                                                     \
-    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) {                                            \
-        ChainKernelArgs<N> a{};                                                                                              \
-        fill_chain_kernel_args(a, ph, dt);                                                                                   \
-        fill_solve_args(a, io, prm);                                                                                         \
-        if (prm.stop_sq_tol < 0.0) {                                                                                         \
-            hipLaunchKernelGGL((dls_chain_hot_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t);           \
-            return hipGetLastError();                                                                                        \
-        }                                                                                                                    \
-        const int64_t rgrid = refill_grid(reinterpret_cast<const void *>(dls_chain_hot_refill_kernel<N, K0, K1, K2>), io.B); \
-        return run_stop_rule(dt.queues, io, prm, stream, a, false, rgrid, PassThrough{&ph, &dt}, [&] {                       \
-            hipLaunchKernelGGL((dls_chain_hot_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t);          \
-            return hipGetLastError();                                                                                        \
-        }, [&](unsigned long long *queue, int chunk) {                                                                       \
-            hipLaunchKernelGGL((dls_chain_hot_refill_kernel<N, K0, K1, K2>), dim3(static_cast<unsigned>(rgrid)), dim3(kBlock), 0, stream, a, t, queue, chunk); \
-            return hipGetLastError();                                                                                        \
-        });                                                                                                                  \
-    }
-    IKGPU_HOT_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_dls_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                                      hipStream_t stream) {
-    if (ph.chain_build == 2) return rtc_launch_chain_hot_track(ph, dt, io, T, prm, stream);
-    const ChainStructure &s = ph.chain_struct;
-    const std::vector<double> &tab = ph.chain_hot;
-    HotTable t{};
-    if (tab.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
-    std::memcpy(t.v, tab.data(), tab.size() * sizeof(double));
-    const dim3 grid(static_cast<unsigned>((io.B + kBlock - 1) / kBlock));
-#define X(N, K0, K1, K2)                                                                                                     \
-    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) {                                            \
-        ChainKernelArgs<N> a{};                                                                                              \
-        fill_chain_kernel_args(a, ph, dt);                                                                                   \
-        fill_solve_args(a, io, prm);                                                                                         \
-        if (prm.stop_sq_tol < 0.0) hipLaunchKernelGGL((dls_chain_hot_track_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t, T); \
-        else hipLaunchKernelGGL((dls_chain_hot_track_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t, T);  \
-        return hipGetLastError();                                                                                            \
-    }
-    IKGPU_HOT_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_dls_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                           const ikgpu_dls_params &prm, hipStream_t stream) {
-    if (ph.chain_build == 2) return rtc_launch_chain_hot_multistart(ph, dt, io, ms, prm, stream);
-    const ChainStructure &s = ph.chain_struct;
-    const std::vector<double> &tab = ph.chain_hot;
-    HotTable t{};
-    if (tab.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
-    std::memcpy(t.v, tab.data(), tab.size() * sizeof(double));
-    const dim3 grid(static_cast<unsigned>(((io.B << ms.log2K) + kBlock - 1) / kBlock));
-#define X(N, K0, K1, K2)                                                                                                     \
-    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) {                                            \
-        ChainKernelArgs<N> a{};                                                                                              \
-        fill_chain_kernel_args(a, ph, dt);                                                                                   \
-        fill_solve_args(a, io, prm);                                                                                         \
-        if (prm.stop_sq_tol < 0.0) hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<N, K0, K1, K2, true>), grid, dim3(kBlock), 0, stream, a, t, ms); \
-        else hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<N, K0, K1, K2, false>), grid, dim3(kBlock), 0, stream, a, t, ms); \
-        return hipGetLastError();                                                                                            \
-    }
+#define X(N, K0, K1, K2) \
+    if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) return launch_hot_shape<N, K0, K1, K2>(ph, dt, io, job, prm, stream, t);
     IKGPU_HOT_SHAPES(X)
 #undef X
     return hipErrorInvalidValue;

@@ -120,33 +120,46 @@ uint64_t fnv1a(uint64_t h, const void *data, size_t n) {
 const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-fast-math", "-ffp-contract=on",
                               "-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"};
 
+// The entry points of a run-time compiled hot module, one row each, in the order of the generated source: hot_source writes the
+// row's wrapper, module_for loads it into HotModule::fn[row], launch_shape launches fn[hot_entry(kind, never-stop)] or the refill row.
+//   extern "C" __global__ <bounds> void <name>(const ikdev::ChainKernelArgs<NJ> a, const ikdev::HotTable t<params>) {
+//       ikdev::<entry><NJ, S<flag>>(a, t<args>);
+//   }
+enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotEntries };
+struct HotEntry {
+    const char *name, *params, *entry, *flag, *args;
+    bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
+};
+const HotEntry kHotEntryTable[kHotEntries] = {
+    {"ikgpu_hot_never", "", "hot_kernel_entry", ", true", "", false},
+    {"ikgpu_hot_stop", "", "hot_kernel_entry", ", false", "", false},
+    {"ikgpu_hot_refill", ", unsigned long long *queue, int chunk", "hot_refill_entry", "", ", queue, chunk", true},
+    // T chained solves in one launch (ikgpu_dls_track_batch)
+    {"ikgpu_hot_track_never", ", const int T", "hot_track_entry", ", true", ", T", false},
+    {"ikgpu_hot_track_stop", ", const int T", "hot_track_entry", ", false", ", T", false},
+    // K starts per problem in one launch, the best one stored (ikgpu_dls_multistart_batch)
+    {"ikgpu_hot_multistart_never", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", true", ", ms", false},
+    {"ikgpu_hot_multistart_stop", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", false", ", ms", false},
+};
+int hot_entry(ChainJob::Kind kind, bool never) {
+    static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
+    return first[kind] + (never ? 0 : 1);
+}
+
 // values: non-structural placement entries of the chain.  The refill kernel asks for two waves per SIMD (256 registers) unless the
-// parked table alone would take most of them.
+// parked table alone would take most of them.  The on-disk cache key hashes this text: one changed byte recompiles every chain that
+// a deployment has precompiled.
 std::string hot_source(int nj, const uint64_t code[3], int values) {
-    char buf[6144];
-    const char *refill_bounds = values <= 40 ? "__launch_bounds__(64, 2)" : "__launch_bounds__(64)";
-    std::snprintf(buf, sizeof buf,
-                  "#include \"chain_hot.hpp\"\n"
-                  "typedef ikdev::ChainStruct<0x%llxull, 0x%llxull, 0x%llxull> S;\n"
-                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_never(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t) {\n"
-                  "    ikdev::hot_kernel_entry<%d, S, true>(a, t);\n}\n"
-                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t) {\n"
-                  "    ikdev::hot_kernel_entry<%d, S, false>(a, t);\n}\n"
-                  "extern \"C\" __global__ %s void ikgpu_hot_refill(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, unsigned long long *queue, int chunk) {\n"
-                  "    ikdev::hot_refill_entry<%d, S>(a, t, queue, chunk);\n}\n"
-                  // T chained solves in one launch (ikgpu_dls_track_batch)
-                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_track_never(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const int T) {\n"
-                  "    ikdev::hot_track_entry<%d, S, true>(a, t, T);\n}\n"
-                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_track_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const int T) {\n"
-                  "    ikdev::hot_track_entry<%d, S, false>(a, t, T);\n}\n"
-                  // K starts per problem in one launch, the best one stored (ikgpu_dls_multistart_batch)
-                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_multistart_never(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const ikdev::MultistartArgs ms) {\n"
-                  "    ikdev::hot_multistart_entry<%d, S, true>(a, t, ms);\n}\n"
-                  "extern \"C\" __global__ __launch_bounds__(64) void ikgpu_hot_multistart_stop(const ikdev::ChainKernelArgs<%d> a, const ikdev::HotTable t, const ikdev::MultistartArgs ms) {\n"
-                  "    ikdev::hot_multistart_entry<%d, S, false>(a, t, ms);\n}\n",
-                  static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]),
-                  nj, nj, nj, nj, refill_bounds, nj, nj, nj, nj, nj, nj, nj, nj, nj, nj);
-    return buf;
+    char head[160];
+    std::snprintf(head, sizeof head, "#include \"chain_hot.hpp\"\ntypedef ikdev::ChainStruct<0x%llxull, 0x%llxull, 0x%llxull> S;\n",
+                  static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]));
+    const std::string n = std::to_string(nj);
+    std::string src = head;
+    for (const HotEntry &e : kHotEntryTable)
+        src += std::string("extern \"C\" __global__ ") + (e.refill_bounds && values <= 40 ? "__launch_bounds__(64, 2)" : "__launch_bounds__(64)") +
+               " void " + e.name + "(const ikdev::ChainKernelArgs<" + n + "> a, const ikdev::HotTable t" + e.params + ") {\n    ikdev::" +
+               e.entry + "<" + n + ", S" + e.flag + ">(a, t" + e.args + ");\n}\n";
+    return src;
 }
 
 // The on-disk cache directory, or "" when there is none this process may trust: code objects read from it are handed to
@@ -228,8 +241,7 @@ struct HotCode {
 };
 struct HotModule {
     hipModule_t mod = nullptr;
-    hipFunction_t never = nullptr, stop = nullptr, refill = nullptr, track_never = nullptr, track_stop = nullptr, multistart_never = nullptr,
-                  multistart_stop = nullptr;
+    hipFunction_t fn[kHotEntries] = {};   // by row of kHotEntryTable
     int refill_waves_per_cu = 0;
 };
 
@@ -494,16 +506,10 @@ bool module_for(const ProblemHost &ph, HotModule &out, hipError_t *err) {
     HotModule &m = g_modules[mkey];
     if (!m.mod) {
         hipError_t e = hipModuleLoadData(&m.mod, hc.code.data());
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.never, m.mod, "ikgpu_hot_never");
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.stop, m.mod, "ikgpu_hot_stop");
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.refill, m.mod, "ikgpu_hot_refill");
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.track_never, m.mod, "ikgpu_hot_track_never");
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.track_stop, m.mod, "ikgpu_hot_track_stop");
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.multistart_never, m.mod, "ikgpu_hot_multistart_never");
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.multistart_stop, m.mod, "ikgpu_hot_multistart_stop");
+        for (int i = 0; i < kHotEntries && e == hipSuccess; ++i) e = hipModuleGetFunction(&m.fn[i], m.mod, kHotEntryTable[i].name);
         if (e == hipSuccess) {
             int per_cu = 0;
-            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.refill, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.fn[kHotRefill], 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
             m.refill_waves_per_cu = per_cu;
         }
         if (e != hipSuccess) { *err = e; m = HotModule{}; return false; }
@@ -522,78 +528,58 @@ int64_t module_refill_waves(int waves_per_cu, int64_t B) {
     return refill_resident(static_cast<int64_t>(waves_per_cu) * cus, B);
 }
 
+// A launch of one of the module's kernels on the kernel-argument segment they share: (ChainKernelArgs<NJ> a, HotTable t), then what the
+// job's kernel takes after them -- nothing, (queue, chunk) for the refill kernel, T, or the multi-start arguments -- at natural
+// alignment.  Each kernel is handed exactly the bytes of its own parameters.
 template <int NJ>
-hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream,
-                        const HotModule &m) {
-    struct Args {   // the kernel-argument segment: (ChainKernelArgs<NJ> a, HotTable t, unsigned long long *queue), natural alignment
+hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
+                        hipStream_t stream, const HotModule &m) {
+    struct Args {
         ikdev::ChainKernelArgs<NJ> a;
         ikdev::HotTable t;
-        unsigned long long *queue;
-        int chunk;
+        union {
+            struct { unsigned long long *queue; int chunk; } refill;
+            int T;
+            ikdev::MultistartArgs ms;
+        } tail;
     } args{};
-    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0, "argument layout");
+    constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
+    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8, "argument layout");
+    constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
+                     kBytesTrack = offsetof(Args, tail.T) + sizeof(int), kBytesMultistart = sizeof(Args);
+    static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
+    static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
+    static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
+    static_assert(kBytesMultistart == kHead + sizeof(ikdev::MultistartArgs), "multi-start: the whole of (a, t, ms)");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
     fill_chain_kernel_args(a, ph, dt);
     fill_solve_args(a, io, prm);
     if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
     std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
 
-    const int64_t waves = (io.B + 63) / 64;
-    auto launch = [&](hipFunction_t fn, int64_t grid, size_t nbytes) {
+    const int64_t waves = (job.lanes(io.B) + 63) / 64;
+    auto launch = [&](int entry, int64_t grid, size_t nbytes) {
         void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
-        return hipModuleLaunchKernel(fn, static_cast<unsigned>(grid), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
+        return hipModuleLaunchKernel(m.fn[entry], static_cast<unsigned>(grid), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
     };
-    const size_t two = offsetof(Args, queue), three = offsetof(Args, chunk) + sizeof(int);
-    if (prm.stop_sq_tol < 0.0) return launch(m.never, waves, two);
+    const bool never = prm.stop_sq_tol < 0.0;
+    const int entry = hot_entry(job.kind, never);
+    if (job.kind == ChainJob::Track) {
+        args.tail.T = job.T;
+        return launch(entry, waves, kBytesTrack);
+    }
+    if (job.kind == ChainJob::Multistart) {
+        args.tail.ms = job.ms;
+        return launch(entry, waves, kBytesMultistart);
+    }
+    if (never) return launch(entry, waves, kBytesPlain);
     const int64_t resident = module_refill_waves(m.refill_waves_per_cu, io.B);
-    return run_stop_rule(dt.queues, io, prm, stream, a, false, resident, PassThrough{&ph, &dt}, [&] { return launch(m.stop, waves, two); },
+    return run_stop_rule(dt.queues, io, prm, stream, a, false, resident, PassThrough{&ph, &dt}, [&] { return launch(entry, waves, kBytesPlain); },
                          [&](unsigned long long *queue, int chunk) {
-                             args.queue = queue;
-                             args.chunk = chunk;
-                             return launch(m.refill, resident, three);
+                             args.tail.refill.queue = queue;
+                             args.tail.refill.chunk = chunk;
+                             return launch(kHotRefill, resident, kBytesRefill);
                          });
-}
-
-// The tracking kernel of the same module: (ChainKernelArgs<NJ> a, HotTable t, int T), one launch.
-template <int NJ>
-hipError_t launch_track_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                              hipStream_t stream, const HotModule &m) {
-    struct Args {
-        ikdev::ChainKernelArgs<NJ> a;
-        ikdev::HotTable t;
-        int T;
-    } args{};
-    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0, "argument layout");
-    fill_chain_kernel_args(args.a, ph, dt);
-    fill_solve_args(args.a, io, prm);
-    if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
-    std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
-    args.T = T;
-    size_t nbytes = offsetof(Args, T) + sizeof(int);
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
-    return hipModuleLaunchKernel(prm.stop_sq_tol < 0.0 ? m.track_never : m.track_stop, static_cast<unsigned>((io.B + 63) / 64), 1, 1, 64, 1, 1, 0,
-                                 stream, nullptr, config);
-}
-
-// The multi-start kernel of the same module: (ChainKernelArgs<NJ> a, HotTable t, MultistartArgs ms), one launch over B x K lanes.
-template <int NJ>
-hipError_t launch_multistart_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                   const ikgpu_dls_params &prm, hipStream_t stream, const HotModule &m) {
-    struct Args {
-        ikdev::ChainKernelArgs<NJ> a;
-        ikdev::HotTable t;
-        ikdev::MultistartArgs ms;
-    } args{};
-    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8, "argument layout");
-    fill_chain_kernel_args(args.a, ph, dt);
-    fill_solve_args(args.a, io, prm);
-    if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
-    std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
-    args.ms = ms;
-    size_t nbytes = sizeof(Args);
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
-    return hipModuleLaunchKernel(prm.stop_sq_tol < 0.0 ? m.multistart_never : m.multistart_stop,
-                                 static_cast<unsigned>(((io.B << ms.log2K) + 63) / 64), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
 }
 
 // ---- the generic lane program specialised for ONE problem (device/generic_solver.hpp with IKD_STATIC_TABLES) -----------------------
@@ -943,44 +929,15 @@ std::string rtc_last_log() {
     return g_last_log;
 }
 
-hipError_t rtc_launch_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream) {
+hipError_t rtc_launch_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
+                                hipStream_t stream) {
     HotModule m;
     {
         hipError_t e = hipSuccess;
         if (!module_for(ph, m, &e)) return e;
     }
     switch (ph.chain.nj) {
-#define X(N) case N: return launch_shape<N>(ph, dt, io, prm, stream, m);
-        X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t rtc_launch_chain_hot_track(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, int T, const ikgpu_dls_params &prm,
-                                      hipStream_t stream) {
-    HotModule m;
-    {
-        hipError_t e = hipSuccess;
-        if (!module_for(ph, m, &e)) return e;
-    }
-    switch (ph.chain.nj) {
-#define X(N) case N: return launch_track_shape<N>(ph, dt, io, T, prm, stream, m);
-        X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t rtc_launch_chain_hot_multistart(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikdev::MultistartArgs &ms,
-                                           const ikgpu_dls_params &prm, hipStream_t stream) {
-    HotModule m;
-    {
-        hipError_t e = hipSuccess;
-        if (!module_for(ph, m, &e)) return e;
-    }
-    switch (ph.chain.nj) {
-#define X(N) case N: return launch_multistart_shape<N>(ph, dt, io, ms, prm, stream, m);
+#define X(N) case N: return launch_shape<N>(ph, dt, io, job, prm, stream, m);
         X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 #undef X
         default: return hipErrorInvalidValue;

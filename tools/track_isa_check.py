@@ -6,7 +6,8 @@
 For every kernel of the file: its loops (a backward branch to a label), innermost first, with their instruction counts and the number
 of v_accvgpr_* instructions inside.  The iteration loop of a chain kernel is its largest loop without a memory instruction; a tracking
 kernel must have none of the parked values' moves in it, and no scratch memory.  With a second file (the same translation unit built from
-the parent commit) it also reports whether every kernel both files have is the same instruction stream."""
+the parent commit) it also reports whether every kernel both files have is the same instruction stream, and lists the kernels only one
+of the two files has: a difference of either sort fails the check."""
 import re
 import sys
 
@@ -86,13 +87,20 @@ def main():
         line = "%-48s %6d instructions, v_accvgpr_* %3d, scratch_* %d" % (short(name), len(idx), total_acc, scratch)
         if inner:
             line += " | iteration loop %5d instructions, v_accvgpr_* inside %d" % (inner[0][2], inner[0][3])
-            if "track" in name and (inner[0][3] or scratch):
+            if "hot_track" in name and (inner[0][3] or scratch):   # (the conditions are the hot builds': some general ones spill SGPRs)
                 bad += 1
         if name in base:
-            _, bidx = loops(instructions(base[name]))
-            line += " | parent: %s" % ("same instruction stream" if bidx == idx else "DIFFERENT (%d instructions)" % len(bidx))
-            bad += bidx != idx
+            # (a label carries the kernel's position in its file, .LBB<position>_<block>: the position is not part of the stream)
+            mine, theirs = ([re.sub(r"\.LBB\d+_", ".LBB_", x) for x in i] for i in (idx, loops(instructions(base[name]))[1]))
+            line += " | parent: %s" % ("same instruction stream" if mine == theirs else "DIFFERENT (%d instructions)" % len(theirs))
+            bad += mine != theirs
         print(line)
+    if len(sys.argv) > 2:   # ... and the two files must hold the same kernels
+        mine, theirs = ({n for n in fs if "kernel" in n} for fs in (new, base))
+        for n in sorted(mine ^ theirs):
+            print("%-48s only in %s" % (short(n), sys.argv[1] if n in mine else sys.argv[2]))
+        print("kernels: %d here, %d in the parent, %d in one file only" % (len(mine), len(theirs), len(mine ^ theirs)))
+        bad += len(mine ^ theirs)
     return 1 if bad else 0
 
 
