@@ -711,6 +711,76 @@ def dls_multistart_batch(problem, Q0, targets, data, visitor=None, p=None, num_s
     return Q, ok, it, win, err
 
 
+def dls_solutions_kernel(data, visitor=None, p=None, num_starts=8):
+    """Name of what dls_solutions_batch runs for these parameters: "dls_chain_solutions<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_solutions_kernel(data._h, C.byref(prm), num_starts).decode()
+
+
+def dls_solutions_batch(problem, Q0, targets, data, visitor=None, p=None, num_starts=8, max_solutions=None, separation=0.1, seed=0, starts=None,
+                        layout="soa", out=None, stream=None):
+    """The distinct solutions among num_starts solves per problem (an IK target rarely has one; ik::dls is a local method: reference
+    ik/ik/dls.cpp:10, :73; the random_restart flag of ik/ik/dls.hpp:27 stays inert).  The starts are dls_multistart_batch's.  In increasing
+    start index, a start is kept when it met the stop rule, fewer than max_solutions (default: num_starts) are kept, and some entry of the
+    task support differs by `separation` (rad or m, plain entries: a full turn apart is a different configuration) or more from every
+    start kept before it.  Each kept Q is bit-identical to dls_batch from that start.  A chain problem with num_starts in {2, 4, ..., 64}
+    runs one launch with the starts of a problem in neighbouring lanes.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], targets [ntasks, 12, B]   |   "aos": Q0 [B, nq], targets [B, ntasks, 12]
+    out: (Q [N, nq, B] | [N, B, nq], count int32 [B], which int32 [N, B], iterations int32 [N, B]) preallocated, or None.
+    Returns (Q, count, which, iterations); slots n >= count[b] of problem b are not written."""
+    import math
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    _check_starts(num_starts)
+    N = num_starts if max_solutions is None else max_solutions
+    if not isinstance(N, int) or not 1 <= N <= num_starts:
+        raise ValueError("max_solutions must be an integer in 1 .. num_starts, got %r" % (max_solutions,))
+    separation = float(separation)
+    if not (math.isfinite(separation) and separation >= 0.0):
+        raise ValueError("separation must be finite and not negative, got %r" % (separation,))
+    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
+    if len(Q0.shape) != 2 or len(targets.shape) != 3:
+        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(targets.shape)))
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
+    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
+        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
+    tensors = [Q0, targets] + ([starts] if starts is not None else [])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
+        raise TypeError("dls_solutions_batch needs float64 CUDA tensors")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError("dls_solutions_batch needs contiguous tensors")
+    if any(t.device.index != data._device for t in tensors):
+        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
+    q_shape = (N,) + tuple(Q0.shape)
+    if out is None:
+        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
+        count = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        which = torch.empty((N, B), dtype=torch.int32, device=Q0.device)
+        it = torch.empty((N, B), dtype=torch.int32, device=Q0.device)
+    else:
+        Q, count, which, it = out
+        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
+        _check_tensor("out[1] (count)", count, (B,), torch.int32, data._device)
+        _check_tensor("out[2] (which)", which, (N, B), torch.int32, data._device)
+        _check_tensor("out[3] (iterations)", it, (N, B), torch.int32, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_solutions_workspace_bytes(data._h, B, num_starts, N, C.byref(prm))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_solutions_batch(data._h, B, num_starts, N, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
+                                           seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), separation, Q.data_ptr(), count.data_ptr(),
+                                           which.data_ptr(), it.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    return Q, count, which, it
+
+
 def _check_tensor(name, t, shape, dtype, device):
     """A device buffer handed to the C ABI as a raw pointer: wrong dtype / device / stride / size would make the kernel read or
     write out of bounds, so it is refused here."""

@@ -36,6 +36,7 @@ SYMBOLS = [
     "ikgpu_dls_solve_batch_sharded", "ikgpu_shard_group_synchronize", "ikgpu_targets_from_pose7",
     "ikgpu_dls_track_batch", "ikgpu_dls_track_kernel",
     "ikgpu_dls_multistart_batch", "ikgpu_dls_multistart_workspace_bytes", "ikgpu_multistart_starts", "ikgpu_dls_multistart_kernel",
+    "ikgpu_dls_solutions_batch", "ikgpu_dls_solutions_workspace_bytes", "ikgpu_dls_solutions_kernel",
 ]
 MAX_PIK_LEVELS, MAX_PIK_DA = 8, 128
 
@@ -156,6 +157,13 @@ def lib():
     L.ikgpu_multistart_starts.restype = C.c_int
     L.ikgpu_dls_multistart_kernel.argtypes = [vp, C.POINTER(DlsParams), i32]
     L.ikgpu_dls_multistart_kernel.restype = C.c_char_p
+    L.ikgpu_dls_solutions_batch.argtypes = [vp, i64, i32, i32, vp, vp, C.c_uint64, vp, C.POINTER(DlsParams), C.c_double, vp, vp, vp, vp, C.c_int, vp,
+                                            C.c_size_t, vp]
+    L.ikgpu_dls_solutions_batch.restype = C.c_int
+    L.ikgpu_dls_solutions_workspace_bytes.argtypes = [vp, i64, i32, i32, C.POINTER(DlsParams)]
+    L.ikgpu_dls_solutions_workspace_bytes.restype = C.c_size_t
+    L.ikgpu_dls_solutions_kernel.argtypes = [vp, C.POINTER(DlsParams), i32]
+    L.ikgpu_dls_solutions_kernel.restype = C.c_char_p
     L.ikgpu_pik_params_default.argtypes = [C.POINTER(PikParams), i32]
     L.ikgpu_pik_params_default.restype = None
     L.ikgpu_pik_solve_batch.argtypes = [vp, i64, vp, vp, C.POINTER(PikParams), vp, vp, vp, C.c_int, vp]

@@ -5,6 +5,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -772,6 +773,23 @@ MultistartWorkspace multistart_workspace(const ikgpu_problem *p, int64_t B) {
     return w;
 }
 
+// The workspace of the solution-set definition run as a loop, carved in this order (each part rounded up to 256 bytes): generated start
+// [nq x B], q of the start's solve [nq x B], its iterations [B], its success flag [B].  The set itself lives in the caller's outputs.
+struct SolutionsWorkspace {
+    size_t start, q, iters, success, total;
+};
+SolutionsWorkspace solutions_workspace(const ikgpu_problem *p, int64_t B) {
+    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+    const size_t b = static_cast<size_t>(B), nq = static_cast<size_t>(p->host.nq);
+    SolutionsWorkspace w{};
+    w.start = 0;
+    w.q = w.start + up(8 * nq * b);
+    w.iters = w.q + up(8 * nq * b);
+    w.success = w.iters + up(4 * b);
+    w.total = w.success + up(b);
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -899,6 +917,76 @@ int ikgpu_dls_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, con
             const ikgpu::MultistartMerge m{B, p->host.nq, p->host.rows, layout, k, q, e, ok, it, key, q_out, success, iters, winner, err_sq};
             const hipError_t em = ikgpu::launch_multistart_merge(m, st);
             if (em != hipSuccess) return named(hip_fail(em, "launching the multi-start merge"));
+        }
+        return static_cast<int>(IKGPU_OK);
+    });
+}
+
+const char *ikgpu_dls_solutions_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    name = variant_kernel_name(p, multistart_fused_log2(p, params, K) >= 0, "_solutions");
+    return name.c_str();
+}
+
+size_t ikgpu_dls_solutions_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, int32_t N, const ikgpu_dls_params *params) {
+    if (!p || !params || B <= 0 || K < 1 || K > 64 || N < 1 || N > K || multistart_fused_log2(p, params, K) >= 0) return 0;
+    return solutions_workspace(p, B).total;
+}
+
+int ikgpu_dls_solutions_batch(const ikgpu_problem *p, int64_t B, int32_t K, int32_t N, const double *q0, const double *starts, uint64_t seed,
+                              const double *targets, const ikgpu_dls_params *params, double sep, double *q_sols, int32_t *count,
+                              int32_t *which, int32_t *iters, int layout, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
+    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (K < 1 || K > 64) return fail(IKGPU_ERR_INVALID, "the number of starts must be 1 .. 64");
+    if (N < 1 || N > K) return fail(IKGPU_ERR_INVALID, "the number of solutions kept must be 1 .. the number of starts");
+    if (!(sep >= 0.0) || !std::isfinite(sep)) return fail(IKGPU_ERR_INVALID, "the separation must be finite and not negative");
+    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_params(params)) return rc;
+    if (params->stop_sq_tol < 0.0 && !ikgpu::visitor_extended(*params))
+        return fail(IKGPU_ERR_INVALID, "the never-stop visitor has no converged start: a solution set needs a stop rule (stop_sq_tol >= 0)");
+    if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
+    if (!q0 || !targets || !q_sols || !count) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (B > (int64_t(1) << 31) * 32 / K) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
+    return guarded([&] {
+        DeviceGuard g(p->device);
+        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        const int log2K = multistart_fused_log2(p, params, K);
+        if (log2K >= 0) {
+            const ikgpu::BatchIO io{B, q0, targets, q_sols, nullptr, iters, layout};
+            ikgpu::ChainJob job{};
+            job.kind = ikgpu::ChainJob::Solutions;
+            job.sol = ikdev::SolutionsArgs{ikdev::MultistartArgs{starts, p->dev.draw, seed, nullptr, nullptr, log2K}, count, which, sep, N};
+            const hipError_t e = ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st);
+            if (e != hipSuccess) return hip_fail(e, "launching the solution-set DLS kernel");
+            return static_cast<int>(IKGPU_OK);
+        }
+        // every other case: the definition itself, start after start on the same stream, inserted into the caller's outputs
+        const SolutionsWorkspace w = solutions_workspace(p, B);
+        if (!workspace || workspace_bytes < w.total)
+            return fail(IKGPU_ERR_INVALID, "solution-set workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                               std::to_string(w.total) + " needed (ikgpu_dls_solutions_workspace_bytes)");
+        char *ws = static_cast<char *>(workspace);
+        double *start = reinterpret_cast<double *>(ws + w.start), *q = reinterpret_cast<double *>(ws + w.q);
+        int32_t *it = reinterpret_cast<int32_t *>(ws + w.iters);
+        uint8_t *ok = reinterpret_cast<uint8_t *>(ws + w.success);
+        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B;
+        for (int k = 0; k < K; ++k) {
+            auto named = [&](int rc) {
+                g_last_error = "start " + std::to_string(k) + ": " + g_last_error;
+                return rc;
+            };
+            const double *from = k == 0 ? q0 : starts ? starts + (k - 1) * q_slab : start;
+            if (k > 0 && !starts) {
+                const hipError_t ed = ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, k, k + 1, q0, seed, start, layout, st);
+                if (ed != hipSuccess) return named(hip_fail(ed, "launching the multi-start draw"));
+            }
+            if (const int rc = dispatch_dls(p, ikgpu::BatchIO{B, from, targets, q, ok, it, layout}, params, st)) return named(rc);
+            const ikgpu::SolutionsInsert m{B, p->host.nq, layout, k, N, sep, p->dev.q_in_chain, q, ok, it, q_sols, count, which, iters};
+            const hipError_t em = ikgpu::launch_solutions_insert(m, st);
+            if (em != hipSuccess) return named(hip_fail(em, "launching the solution-set insert"));
         }
         return static_cast<int>(IKGPU_OK);
     });

@@ -474,6 +474,36 @@ IKD_FN void hot_multistart_body(const ChainKernelArgs<NJ> &a, const MultistartAr
                          [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
 }
 
+// K starts per problem, the distinct converged ones stored -- dls_chain_solutions_body (chain_kernel_body.hpp: the definition, the lane
+// mapping, the three pieces) with the hot program: the unchanged hot_dls, always under a stop rule (without one no start converges).
+template <int NJ, class S, class Tab, class AnyFn>
+IKD_FN void hot_solutions_lane(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, const Tab &t, int64_t b, int k, double (&q)[NJ],
+                               bool &success, int &iters, AnyFn any_active) {
+    multistart_load(a, sa.ms, b, k, q);
+    double oMt[12];
+    load_target(a, b, oMt);
+    hot_dls<NJ, S, false>(t, a.prm, q, oMt, iters, success, any_active);
+}
+
+template <int NJ, class S, class Tab, class AnyFn, class Fetch>
+IKD_FN void hot_solutions_body(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, const Tab &t, int64_t gid, AnyFn any_active, Fetch fetch) {
+    const int64_t prob = gid >> sa.ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << sa.ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ];
+    bool success;
+    int iters;
+    hot_solutions_lane<NJ, S>(a, sa, t, b, k, q, success, iters, any_active);
+    SolutionsLane s;
+    solutions_select<NJ>(s, sa.ms.log2K, k, sa.N, sa.sep, success, q, fetch);
+    if (!valid) return;
+    if (s.kept)
+        solutions_store(a, sa, b, k, s.slot, q, iters,
+                        [&](const double *src, double *q_out, bool stepped) { hot_pass_through_from(a, src, q_out, b, stepped); });
+    if (k == 0) sa.count[b] = s.cnt;
+}
+
 #if IKD_HIP_LANG
 // ---- kernel entries, shared by the instantiations compiled into the library (kernels_hot.hip) and the ones compiled at run time for
 // a chain's own structure code (rtc.cpp) -----------------------------------------------------------------------------------------
@@ -520,6 +550,15 @@ __device__ __forceinline__ void hot_multistart_entry(const ChainKernelArgs<NJ> &
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
     hot_multistart_body<NJ, S, NEVERSTOP>(a, ms, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
+}
+
+template <int NJ, class S>
+__device__ __forceinline__ void hot_solutions_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const SolutionsArgs &sa) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    HotTable tv;
+    hot_park_table<NJ, S>(t, tv);
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    hot_solutions_body<NJ, S>(a, sa, tv, gid, KeepGoing{0, 0, 0}, SolutionsShuffle{lane & ~((1 << sa.ms.log2K) - 1)});
 }
 
 template <int NJ, class S>

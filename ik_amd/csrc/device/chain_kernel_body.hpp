@@ -8,6 +8,7 @@
 
 #include "chain_solver.hpp"
 #include "multistart.hpp"
+#include "solutions.hpp"
 
 namespace ikdev {
 
@@ -263,6 +264,68 @@ IKD_FN void dls_chain_multistart_body(const ChainKernelArgs<NJ> &a, const Multis
     const int win = multistart_select(ms.log2K, multistart_key(success, err_sq), k, exchange);
     if (valid && win == k)
         multistart_store(a, ms, b, k, q, success, iters, err_sq, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
+}
+
+// ---- solution set: K starts per problem in one launch, the distinct converged ones stored (include/ikgpu.h ikgpu_dls_solutions_batch) ---
+// Defined through the K single solves of the multi-start call (the same starts, the same lane mapping: lane gid serves problem
+// gid >> log2K with start gid & (K - 1)) and the greedy rule of device/solutions.hpp over their results: start k is kept when it met the
+// stop rule, fewer than N are kept, and some chain entry differs by sep or more from every start kept before it.  Three pieces again: the
+// lane's own solve, the K steps of the set (solutions_offer / solutions_take) and a kept lane's stores (solutions_store).
+
+// Entries outside the task support of a solve started from column b of `src`, into a slab of its own (chain_pass_through_from).
+template <int NJ>
+IKD_FN void chain_pass_through_into(const ChainKernelArgs<NJ> &a, const double *src, double *q_out, int64_t b, bool stepped) {
+    for (int i = 0; i < a.nq; ++i) {
+        if (a.q_in_chain[i]) continue;
+        const double v = src[at(a.layout, a.B, a.nq, i, b)];
+        const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
+        q_out[at(a.layout, a.B, a.nq, i, b)] = stepped ? c : v;
+    }
+}
+
+// One start: the single solve's loop, unchanged.  (Only converged starts matter: no evaluation after it.)
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN void dls_chain_solutions_lane(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, const Desc &d, int64_t b, int k, double (&q)[NJ],
+                                     bool &success, int &iters, AnyFn any_active) {
+    multistart_load(a, sa.ms, b, k, q);
+    double oMt[12];
+    load_target(a, b, oMt);
+    chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active);
+}
+
+// A kept lane's stores into slab `slot` of q_sols (a.q_out) / which / iters (a.iters): what the single solve from start k writes, over
+// all nq entries.  pass(src, q_out, stepped) writes the entries outside the chain from the start's own column; it goes FIRST: its loads
+// are the only ones after the loop, and behind a store their wait would be for the store's acknowledgement as well (loads and stores
+// share one counter on gfx950).
+template <int NJ, class Pass>
+IKD_FN void solutions_store(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, int64_t b, int k, int slot, const double (&q)[NJ], int iters,
+                            Pass pass) {
+    double *q_out = a.q_out + static_cast<int64_t>(slot) * a.nq * a.B;
+    pass(multistart_source(a, sa.ms, k), q_out, iters > 0);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+    if (sa.which) sa.which[slot * a.B + b] = k;
+    if (a.iters) a.iters[slot * a.B + b] = iters;
+}
+
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn, class Fetch>
+IKD_FN void dls_chain_solutions_body(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, const Desc &d, int64_t gid, AnyFn any_active,
+                                     Fetch fetch) {
+    const int64_t prob = gid >> sa.ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << sa.ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ];
+    bool success;
+    int iters;
+    dls_chain_solutions_lane<NJ, KT, SMASK>(a, sa, d, b, k, q, success, iters, any_active);
+    SolutionsLane s;
+    solutions_select<NJ>(s, sa.ms.log2K, k, sa.N, sa.sep, success, q, fetch);
+    if (!valid) return;
+    if (s.kept)
+        solutions_store(a, sa, b, k, s.slot, q, iters,
+                        [&](const double *src, double *q_out, bool stepped) { chain_pass_through_into(a, src, q_out, b, stepped); });
+    if (k == 0) sa.count[b] = s.cnt;
 }
 
 #if IKD_HIP_LANG

@@ -728,6 +728,30 @@ inline void dls_multistart_device(InverseKinematicsProblem &problem, std::int64_
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// The distinct solutions among K starts per problem on DEVICE buffers (the starts are dls_multistart_device's; ik::dls is a local method:
+// ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 stays inert).  In increasing start index a start is kept when it met the stop rule, fewer than N
+// are kept, and some entry of the task support differs by `separation` or more from every start kept before it.  count [B]; for
+// n < count[b], slab n of Q [N][nq][B] is bit-identical to dls_batch_device from start which[n][b]; which / iterations [N][B] may be null.
+// workspace: device memory of solutions_workspace_bytes() bytes (0 for a chain problem with K in {2, 4, .., 64}: one launch).
+inline std::size_t solutions_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, int K, int N, dls_data &data,
+                                             const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                             const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_solutions_workspace_bytes(data.handle(), B, K, N, &prm);
+}
+inline void dls_solutions_device(InverseKinematicsProblem &problem, std::int64_t B, int K, int N, const number_t *Q0, const number_t *starts,
+                                 std::uint64_t seed, const number_t *targets, dls_data &data, number_t separation, number_t *Q, std::int32_t *count,
+                                 std::int32_t *which, std::int32_t *iterations, void *workspace, std::size_t workspace_bytes, void *stream,
+                                 const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                 const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_solutions_batch(data.handle(), B, K, N, Q0, starts, seed, targets, &prm, separation, Q, count, which, iterations, IKGPU_SOA,
+                                  workspace, workspace_bytes, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // ---- ik::pik, the prioritised solver (ik/ik/pik.hpp:11-59; ik/ik/pik.cpp:31-103) ---------------------
 struct pik_parameters {  // ik/ik/pik.hpp:11-16; the reference loop reads neither damping nor max_time
     int max_iterations = 100;

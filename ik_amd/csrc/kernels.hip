@@ -86,6 +86,17 @@ __global__ __launch_bounds__(kBlock) void dls_chain_multistart_kernel(const Chai
     ikdev::dls_chain_multistart_body<NJ, KT, SMASK>(a, ms, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
 }
 
+// K starts per problem in one launch, the distinct converged ones stored (device/chain_kernel_body.hpp dls_chain_solutions_body): the
+// general build's solution-set kernel.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_solutions_kernel(const ChainKernelArgs<NJ> a, const ikdev::SolutionsArgs sa) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    ikdev::dls_chain_solutions_body<NJ, KT, SMASK>(a, sa, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0},
+                                                   ikdev::SolutionsShuffle{lane & ~((1 << sa.ms.log2K) - 1)});
+}
+
 struct MultistartStartsArgs {
     const double *q0, *lower, *upper;
     const uint8_t *draw;
@@ -122,6 +133,28 @@ __global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m)
     if (m.iters_out) m.iters_out[b] = m.iters[b];
     if (m.winner) m.winner[b] = m.k;
     if (m.err_sq) m.err_sq[b] = err;
+}
+
+__global__ __launch_bounds__(256) void solutions_insert(const SolutionsInsert m) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= m.B) return;
+    const int n = m.k == 0 ? 0 : m.count[b];
+    if (m.k == 0) m.count[b] = 0;
+    if (!m.success[b] || n >= m.N) return;
+    const int64_t slab = static_cast<int64_t>(m.nq) * m.B;
+    for (int s = 0; s < n; ++s) {
+        bool near = true;
+        for (int i = 0; i < m.nq; ++i) {
+            if (!m.support[i]) continue;
+            const int64_t at = ikdev::at(m.layout, m.B, m.nq, i, b);
+            near = near && !(__builtin_fabs(m.q[at] - m.q_sols[s * slab + at]) >= m.sep);
+        }
+        if (near) return;
+    }
+    for (int i = 0; i < m.nq; ++i) m.q_sols[n * slab + ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
+    if (m.which) m.which[n * m.B + b] = m.k;
+    if (m.iters_out) m.iters_out[n * m.B + b] = m.iters[b];
+    m.count[b] = n + 1;
 }
 
 struct PassThroughArgs {
@@ -208,7 +241,9 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         constexpr int SM = decltype(smask)::value;
         if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
         const dim3 grid = grid_for(job.lanes(io.B));
+        if (job.kind == ChainJob::Solutions && prm.stop_sq_tol < 0.0) return hipErrorInvalidValue;
         if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
+        else if (job.kind == ChainJob::Solutions) hipLaunchKernelGGL((dls_chain_solutions_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.sol);
         else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.ms);
         return hipGetLastError();
     });
@@ -390,6 +425,11 @@ hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, i
 
 hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream) {
     hipLaunchKernelGGL(multistart_merge, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_solutions_insert(const SolutionsInsert &m, hipStream_t stream) {
+    hipLaunchKernelGGL(solutions_insert, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "device/multistart.hpp"
+#include "device/solutions.hpp"
 #include "problem.hpp"
 
 namespace ikgpu {
@@ -73,12 +74,18 @@ struct BatchIO {
 //               targets / q_out / success / iters follows at k times the slab's size.
 //   Multistart: K = 1 << ms.log2K starts per problem in ONE launch, the best one stored (ikgpu_dls_multistart_batch;
 //               dls_chain_multistart_body, hot_multistart_body): B x K lanes, problem gid / K with start gid % K.
-// Track and Multistart are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is capturable.
+//   Solutions:  the same B x K lanes, the distinct converged starts stored, up to sol.N per problem (ikgpu_dls_solutions_batch;
+//               dls_chain_solutions_body, hot_solutions_body): `io.q_out` / `io.iters` are [N] slabs, `io.success` is not written.  Needs a
+//               stop rule (the never-stop visitor converges nowhere): a launcher refuses the job without one.
+// Track, Multistart and Solutions are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is capturable.
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart } kind = Solve;
+    enum Kind { Solve, Track, Multistart, Solutions } kind = Solve;
     int T = 0;                     // Track: the number of waypoints
     ikdev::MultistartArgs ms{};    // Multistart
-    int64_t lanes(int64_t B) const { return kind == Multistart ? B << ms.log2K : B; }   // one lane per problem, or per start
+    ikdev::SolutionsArgs sol{};    // Solutions
+    int64_t lanes(int64_t B) const {   // one lane per problem, or per start
+        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : B;
+    }
 };
 
 // Returns hipSuccess or the launch error. Throws std::runtime_error for an un-instantiated shape.
@@ -106,6 +113,22 @@ struct MultistartMerge {
     double *err_sq;
 };
 hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream);
+// One step of the solution-set definition run as a loop: start k's single solve (q / success / iters) against the set so far in the
+// caller's outputs -- slots 0 .. count[b]-1 of q_sols.  Inserted into slot count[b] when it succeeded, count[b] < N and some support
+// entry differs by sep or more from every slot; k == 0 initialises count.
+struct SolutionsInsert {
+    int64_t B;
+    int nq, layout, k, N;
+    double sep;
+    const uint8_t *support;   // [nq] (DeviceTables::q_in_chain)
+    const double *q;
+    const uint8_t *success;
+    const int32_t *iters;
+    double *q_sols;           // [N][nq x B]
+    int32_t *count;           // [B]
+    int32_t *which, *iters_out;   // null or [N][B]
+};
+hipError_t launch_solutions_insert(const SolutionsInsert &m, hipStream_t stream);
 bool chain_shape_built(int nj, int type);
 // The structure-specialised builds of the chain kernel (kernels_hot.hip, device/chain_hot.hpp): one Full task with unit
 // weights on a chain whose placement-structure code has an instantiation.  launch_dls_chain takes that route when it exists.

@@ -55,6 +55,13 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_multistart_kernel(const 
     ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms);
 }
 
+// K starts per problem in one launch, the distinct converged ones stored (device/chain_hot.hpp hot_solutions_body; include/ikgpu.h
+// ikgpu_dls_solutions_batch): the multi-start kernel's lane mapping.  Stop rule only; lock-step; no LDS, no queue slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_solutions_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::SolutionsArgs sa) {
+    ikdev::hot_solutions_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, sa);
+}
+
 // X(NJ, code0, code1, code2)
 #define IKGPU_HOT_SHAPES(X)                                                                                                   \
     X(7, 0x04f0208cce8c7664ull, 0x395959cacad65656ull, 0x000001cacace5656ull) /* Cassie leg: Left / RightFootFront, 22 values */ \
@@ -110,6 +117,9 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
             hipLaunchKernelGGL((dls_chain_hot_track_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.T);
         } else if (job.kind == ChainJob::Multistart) {
             hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.ms);
+        } else if (job.kind == ChainJob::Solutions) {
+            if constexpr (NEVER) return hipErrorInvalidValue;   // (no start converges without a stop rule: the entry point refuses the call)
+            else hipLaunchKernelGGL((dls_chain_hot_solutions_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.sol);
         } else if constexpr (NEVER) {
             hipLaunchKernelGGL((dls_chain_hot_kernel<NJ, C0, C1, C2, true>), grid, block, 0, stream, a, t);
         } else {

@@ -58,6 +58,7 @@
 IKGPU_EMBED(ikgpu_src_lane_math, "device/lane_math.hpp")
 IKGPU_EMBED(ikgpu_src_chain_solver, "device/chain_solver.hpp")
 IKGPU_EMBED(ikgpu_src_multistart, "device/multistart.hpp")
+IKGPU_EMBED(ikgpu_src_solutions, "device/solutions.hpp")
 IKGPU_EMBED(ikgpu_src_chain_kernel_body, "device/chain_kernel_body.hpp")
 IKGPU_EMBED(ikgpu_src_chain_hot, "device/chain_hot.hpp")
 IKGPU_EMBED(ikgpu_src_tree_solver, "device/tree_solver.hpp")
@@ -125,7 +126,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 //   extern "C" __global__ <bounds> void <name>(const ikdev::ChainKernelArgs<NJ> a, const ikdev::HotTable t<params>) {
 //       ikdev::<entry><NJ, S<flag>>(a, t<args>);
 //   }
-enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotEntries };
+enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotSolutionsStop, kHotEntries };
 struct HotEntry {
     const char *name, *params, *entry, *flag, *args;
     bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
@@ -140,8 +141,12 @@ const HotEntry kHotEntryTable[kHotEntries] = {
     // K starts per problem in one launch, the best one stored (ikgpu_dls_multistart_batch)
     {"ikgpu_hot_multistart_never", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", true", ", ms", false},
     {"ikgpu_hot_multistart_stop", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", false", ", ms", false},
+    // ... the distinct converged ones stored (ikgpu_dls_solutions_batch): a stop rule always, so one entry
+    {"ikgpu_hot_solutions_stop", ", const ikdev::SolutionsArgs sa", "hot_solutions_entry", "", ", sa", false},
 };
+// The row of a job, or -1: a solution-set job has no never-stop entry.
 int hot_entry(ChainJob::Kind kind, bool never) {
+    if (kind == ChainJob::Solutions) return never ? -1 : kHotSolutionsStop;
     static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
     return first[kind] + (never ? 0 : 1);
 }
@@ -261,6 +266,7 @@ struct Hdr { const char *name, *begin, *end; };
 const Hdr kHeaders[] = {{"lane_math.hpp", ikgpu_src_lane_math, ikgpu_src_lane_math_end},
                         {"chain_solver.hpp", ikgpu_src_chain_solver, ikgpu_src_chain_solver_end},
                         {"multistart.hpp", ikgpu_src_multistart, ikgpu_src_multistart_end},
+                        {"solutions.hpp", ikgpu_src_solutions, ikgpu_src_solutions_end},
                         {"chain_kernel_body.hpp", ikgpu_src_chain_kernel_body, ikgpu_src_chain_kernel_body_end},
                         {"chain_hot.hpp", ikgpu_src_chain_hot, ikgpu_src_chain_hot_end},
                         {"tree_solver.hpp", ikgpu_src_tree_solver, ikgpu_src_tree_solver_end},
@@ -541,16 +547,20 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
             struct { unsigned long long *queue; int chunk; } refill;
             int T;
             ikdev::MultistartArgs ms;
+            ikdev::SolutionsArgs sa;
         } tail;
     } args{};
     constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
-    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8, "argument layout");
+    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8 &&
+                      alignof(ikdev::SolutionsArgs) == 8, "argument layout");
     constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
-                     kBytesTrack = offsetof(Args, tail.T) + sizeof(int), kBytesMultistart = sizeof(Args);
+                     kBytesTrack = offsetof(Args, tail.T) + sizeof(int),
+                     kBytesMultistart = offsetof(Args, tail) + sizeof(ikdev::MultistartArgs), kBytesSolutions = sizeof(Args);
     static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
     static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
     static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
     static_assert(kBytesMultistart == kHead + sizeof(ikdev::MultistartArgs), "multi-start: the whole of (a, t, ms)");
+    static_assert(kBytesSolutions == kHead + sizeof(ikdev::SolutionsArgs), "solution set: the whole of (a, t, sa)");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
     fill_chain_kernel_args(a, ph, dt);
     fill_solve_args(a, io, prm);
@@ -564,6 +574,11 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     };
     const bool never = prm.stop_sq_tol < 0.0;
     const int entry = hot_entry(job.kind, never);
+    if (entry < 0) return hipErrorInvalidValue;
+    if (job.kind == ChainJob::Solutions) {
+        args.tail.sa = job.sol;
+        return launch(entry, waves, kBytesSolutions);
+    }
     if (job.kind == ChainJob::Track) {
         args.tail.T = job.T;
         return launch(entry, waves, kBytesTrack);

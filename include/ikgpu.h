@@ -277,6 +277,46 @@ int ikgpu_multistart_starts(const ikgpu_problem *p, int64_t B, int32_t K, const 
  * ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- and has no such choice.) */
 const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K);
 
+/* ---- solution set: the DISTINCT converged starts among K starts per problem, up to N of them.  An IK target rarely has one solution
+ * (a 6-joint arm has up to eight branches, a 7-joint chain a whole family) and ik::dls, a local method, finds the one its start leads
+ * to (reference ik/ik/dls.cpp:10 "todo - if limited convergence, try random walk"; dls.cpp:73 "If issues, perform random restart";
+ * dls_parameters::random_restart, ik/ik/dls.hpp:27, is a flag nothing reads -- it stays inert here too).  1 <= N <= K <= 64, sep finite
+ * and >= 0, else IKGPU_ERR_INVALID.  DEFINED through K calls of ikgpu_dls_solve_batch with the same targets and params:
+ *   the starts are exactly those of ikgpu_dls_multistart_batch: start 0 of problem b is its column of q0; start k >= 1 is slab k-1 of
+ *   `starts` ([K-1][nq x B]) when starts != NULL, else the generated start ikgpu_multistart_starts writes for (seed, b, k);
+ *   r_k = (q_k, success_k, iters_k) is what the single solve writes from start k;
+ *   the KEPT set of problem b is built greedily in increasing k: start k is kept if and only if success_k is true, fewer than N starts
+ *   are kept so far, and for every kept j < k there is an entry i with ikgpu_problem_support = 1 and |q_k[i] - q_j[i]| >= sep (one
+ *   IEEE subtraction, fabs and a compare: reproducible bit for bit from the single solves).
+ * The comparison is over plain entries: configurations that differ by a full turn of a joint are DIFFERENT configurations (they are
+ * to a joint-limited robot); distance modulo 2 pi is not taken.  sep == 0 keeps every converged start, up to N.
+ *   count  [B]             the number kept, at most N
+ *   q_sols [N][nq x B]     each slab in the batch layout; for n < count[b], slab n holds q of the n-th kept start, bit-identical over all
+ *                          nq entries to the single solve from that start (entries outside the support come from that start's own
+ *                          column, clipped once a step was taken)
+ *   which  [N][B], iters [N][B]   the n-th kept start's index and its iteration count; either may be NULL
+ * Slots n >= count[b] are not written.  count and q_sols may not be NULL.  DEVICE pointers; asynchronous on `stream`; B == 0 is a
+ * no-op.  q_sols must not overlap q0 or starts.  Under the never-stop visitor (stop_sq_tol < 0 and no derived visitor) no start
+ * converges by construction: IKGPU_ERR_INVALID.
+ * A chain problem under the reference's visitor with K in {2, 4, 8, 16, 32, 64} runs ONE launch (`dls_chain_solutions<...>`) with the
+ * multi-start kernel's lane mapping: the K lanes of a group build the set across lanes after the loop, and every kept lane stores
+ * into its slot (no LDS, no queue slot, no allocation: capturable in a graph; `workspace` is not read).  Every other case -- tree,
+ * generic, static-program and derived-visitor problems, K = 1, K not a power of two -- runs the definition from inside the call, start
+ * after start, in `workspace` (DEVICE memory of at least ikgpu_dls_solutions_workspace_bytes bytes, else IKGPU_ERR_INVALID); when a
+ * step fails, ikgpu_last_error() names the start. */
+int ikgpu_dls_solutions_batch(const ikgpu_problem *p, int64_t B, int32_t K, int32_t N, const double *q0, const double *starts,
+                              uint64_t seed, const double *targets, const ikgpu_dls_params *params, double sep, double *q_sols,
+                              int32_t *count, int32_t *which, int32_t *iters, int layout /* ikgpu_layout */, void *workspace,
+                              size_t workspace_bytes, void *stream);
+/* Bytes of `workspace` ikgpu_dls_solutions_batch needs for these arguments: 0 for the single launch.  (The restarts the reference only
+ * plans -- ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- need no memory there either: this serves the loop that stands in for them.) */
+size_t ikgpu_dls_solutions_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, int32_t N, const ikgpu_dls_params *params);
+/* Name of what ikgpu_dls_solutions_batch runs with these parameters and K: `dls_chain_solutions<NJ=7,full,hot>` (or hot-rtc / general:
+ * the build ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the definition run start
+ * after start.  The string belongs to the calling thread and lasts until its next call.  (The reference plans its restarts --
+ * ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- and has no such choice.) */
+const char *ikgpu_dls_solutions_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K);
+
 /* FrameTask::target (an SE(3), reference ik/ik/frame.hpp:189) given as 7 doubles -- translation (x y z), quaternion (qx qy qz qw;
  * converted as Eigen's toRotationMatrix does, i.e. as the free-flyer's configuration is read) -- expanded into the 12-double slots
  * the solve entry points take.  pose7: [ntasks x 7 x B] (IKGPU_SOA) or [B x ntasks x 7] (IKGPU_AOS); targets12 likewise with 12.
