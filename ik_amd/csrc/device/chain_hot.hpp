@@ -2,9 +2,10 @@
 // frame fixed in the world) on a serial chain of NJ <= 7 revolute joints, specialised at compile time on the STRUCTURE of the
 // chain's constant placements.
 //
-// Same algorithm and the same arithmetic as device/chain_solver.hpp (which stays the program of every other chain problem;
-// the reference path it restates is cited there: ik/ik/dls.cpp:5-78, data.cpp:25-58, frame.hpp:37-62,152-182,
-// common.hpp:53-56, visitor.hpp:15-21).  What differs is only what a lone wave pays for: measured on gfx950
+// Same algorithm as device/chain_solver.hpp (which stays the program of every other chain problem; the reference path it
+// restates is cited there: ik/ik/dls.cpp:5-78, data.cpp:25-58, frame.hpp:37-62,152-182, common.hpp:53-56, visitor.hpp:15-21),
+// with the Jacobian columns built in the task frame, tip to base (hot_evaluate): the two builds differ by rounding.
+// What differs is what a lone wave pays for: measured on gfx950
 // (tools/issue_probe.hip, profiles/r02_issue_probe.csv) a wave that has its SIMD to itself -- the situation at the metric's
 // batch, 65536 problems = 1024 waves on 1024 SIMDs -- issues ONE instruction of any kind every 4 cycles (VALU, SALU, s_nop,
 // s_waitcnt alike; 16 for an FP64 transcendental, 8 for v_mov_b64) and a dependent FP64 instruction can follow its producer
@@ -22,6 +23,12 @@
 //    loads, no s_waitcnt inside the iteration.  A model whose code has no instantiation runs on chain_solver.hpp.
 //  * The visitor that never stops (the metric's fixed-iteration mode) is its own instantiation: no `active` selects, no
 //    stop-test arithmetic.
+//  * The task Jacobian in the task frame, tip to base (hot_evaluate).  The reference defines J = -Jlog6(tMf) J_local with the frame
+//    Jacobian in the LOCAL frame; walking the chain from the task frame towards the base yields the columns of J_local directly
+//    (third row of the running rotation, and R^T (e_z x p)).  The world-frame form of chain_solver.hpp pays for the detour: the
+//    frame rotation folded into both Jlog6 blocks (54 multiply-adds), org_j - p and a full cross product per joint, and three
+//    multiply-adds per non-zero translation component of a right-multiplied placement where the left-multiplied one adds.  Issue
+//    slots per iteration of the evaluation (tools/hot_phase_count.py): Cassie leg 743 -> 641, UR5 / UR10 653 -> 611.
 #pragma once
 #if !defined(__HIPCC_RTC__)
 #include <cstdint>
@@ -81,6 +88,13 @@ struct ChainRuns {
 
 constexpr int kHotTableMax = 112;  // doubles in the kernel-argument copy of the compact table (values, then lo[NJ], hi[NJ]): 8 x 12 + 2 x 7 when nothing is structural
 
+// Placement values (S::offset(NJ + 1) doubles) up to which hot_park_table's copy of the table stays in vector registers next to the
+// loop's own live registers: the built-in structure codes have at most 36 (Cassie leg: 22) and stay, the all-general 7-joint chain
+// has 96 and is parked in accumulation registers by the compiler (compile-only assembly, tools/kernel_stats.py).  The bound sits
+// between the two observed classes -- nothing between 36 and 96 has been built --; it is the one place that says which class a chain
+// is in, and hot_evaluate asks it.
+constexpr int kHotTableVgprMax = 48;
+
 struct HotTable {
     double v[kHotTableMax];
 };
@@ -91,56 +105,76 @@ IKD_FN double hot_rot(const Tab &t, int e) {
     return S::ent(I, e) == kEntGeneral ? t.v[S::rot_at(I, e)] : S::literal(I, e);
 }
 
-// (R, p) <- (R, p) * placement I.  Written as the general product; with literal zeros and ones in it the compiler folds the
-// multiplications by 1 and (under -fno-signed-zeros -fno-honor-nans) by 0 away: same bits as the full product on finite data.
+// (R, p) <- placement I * (R, p), a LEFT composition: R' = Rc R, p' = Rc p + tc.  Written as the general product; with literal zeros
+// and ones in it the compiler folds the multiplications by 1 and (under -fno-signed-zeros -fno-honor-nans) by 0 away: same bits as
+// the full product on finite data.  The translation is the innermost addend: under a near-permutation Rc it is one addition per
+// non-zero component (composed from the right it went through the running rotation, three multiply-adds per component), and an
+// identity Rc leaves R -- its third row in particular -- the very same values.
 template <class S, int I, class Tab>
-IKD_FN void hot_compose(double (&R)[9], double (&p)[3], const Tab &t) {
+IKD_FN void hot_compose_left(double (&R)[9], double (&p)[3], const Tab &t) {
+    double Ro[9], po[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (S::tnz(I, k)) {
-            const double tk = t.v[S::trans_at(I, k)];
+    for (int k = 0; k < 9; ++k) Ro[k] = R[k];
 #pragma unroll
-            for (int r = 0; r < 3; ++r) p[r] = dfma(R[3 * r + k], tk, p[r]);
-        }
-    }
+    for (int k = 0; k < 3; ++k) po[k] = p[k];
+    // row by row of Rc: three entries of R' and one of p' per row
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        const double a = R[3 * r], b = R[3 * r + 1], d = R[3 * r + 2];
+        const double c0 = hot_rot<S, I>(t, 3 * r), c1 = hot_rot<S, I>(t, 3 * r + 1), c2 = hot_rot<S, I>(t, 3 * r + 2);
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-            R[3 * r + k] = dfma(a, hot_rot<S, I>(t, k), dfma(b, hot_rot<S, I>(t, 3 + k), d * hot_rot<S, I>(t, 6 + k)));
+        for (int k = 0; k < 3; ++k) R[3 * r + k] = dfma(c0, Ro[k], dfma(c1, Ro[3 + k], c2 * Ro[6 + k]));
+        const double last = S::tnz(I, r) ? dfma(c2, po[2], t.v[S::trans_at(I, r)]) : c2 * po[2];
+        p[r] = dfma(c0, po[0], dfma(c1, po[1], last));
     }
 }
 
-// e (6) and the NEGATED task Jacobian columns at q (see chain_evaluate in chain_solver.hpp: same expressions, KT_FULL,
-// unit weights).  oMt: target placement in the world.
+// e = log6(fMt) (6) and the NEGATED task Jacobian columns col[j] = Jlog6(tMf) J_local(:, j) at q (KT_FULL, unit weights; the
+// reference defines J = -Jlog6 J_local with the frame Jacobian in the LOCAL frame, ik/ik/frame.hpp:162-166).  oMt: target placement
+// in the world.  The chain oMf = P_0 Rz(q_0) P_1 Rz(q_1) ... P_{NJ-1} Rz(q_{NJ-1}) P_NJ is walked from the TIP to the base: the running
+// Y = (R, p) = [Rz(q_j)] P_{j+1} ... P_NJ maps task-frame coordinates into joint j's frame, so joint j's column of J_local is read off
+// it directly -- the unit twist about z carried to the task frame by Y^-1:  angular part R^T e_z, the third row of R;  linear part
+// R^T (e_z x p).  (chain_solver.hpp walks base to tip in the world frame and then rotates everything into the task frame: there the
+// frame rotation is folded into both Jlog6 blocks, 54 multiply-adds, and every column pays org_j - p and a full cross product.)
+// INVARIANT hot_gram and hot_step rely on: inside a run of identity-rotation placements (S::leader) the angular parts ang[j], and so
+// col[j][3..5], are the SAME values for every member -- rot_z_left leaves row 2 of R alone and an identity Rc folds away in
+// hot_compose_left, so the members read the same registers.
 template <int NJ, class S, class Tab>
 IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt)[12], double (&e)[6], double (&col)[NJ][6]) {
-    double zax[NJ][3], org[NJ][3];
-    double R[9], p[3];
-    // placement 0: world -> joint-0 frame
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = hot_rot<S, 0>(t, k);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = S::tnz(0, k) ? t.v[S::trans_at(0, k)] : 0.0;
-
     // the NJ sin / cos first: independent of the chain, the constants are live once
     double sn[NJ], cs[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) dsincos_hot(q[j], sn[j], cs[j]);
 
-#define IKD_HOT_JOINT(J)                                                   \
-    if (J < NJ) {                                                          \
-        if (J > 0) hot_compose<S, (J < NJ ? J : 0)>(R, p, t);              \
-        rot_z_right(R, sn[J < NJ ? J : 0], cs[J < NJ ? J : 0]);            \
-        zax[J < NJ ? J : 0][0] = R[2]; zax[J < NJ ? J : 0][1] = R[5]; zax[J < NJ ? J : 0][2] = R[8]; \
-        org[J < NJ ? J : 0][0] = p[0]; org[J < NJ ? J : 0][1] = p[1]; org[J < NJ ? J : 0][2] = p[2]; \
-    }
-    IKD_HOT_JOINT(0) IKD_HOT_JOINT(1) IKD_HOT_JOINT(2) IKD_HOT_JOINT(3) IKD_HOT_JOINT(4) IKD_HOT_JOINT(5) IKD_HOT_JOINT(6)
-#undef IKD_HOT_JOINT
-    hot_compose<S, NJ>(R, p, t);
+    double ang[NJ][3], lin[NJ][3];
+    double R[9], p[3];
+    // placement NJ: last joint frame -> task frame
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = hot_rot<S, NJ>(t, k);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = S::tnz(NJ, k) ? t.v[S::trans_at(NJ, k)] : 0.0;
 
-    // fMt = oMf^-1 oMt
+    // A chain with more than kHotTableVgprMax placement values has its table parked in accumulation registers (hot_park_table: more
+    // values than the vector registers hold).  The rotation of Y and its translation are two independent dependency chains, and the compiler was seen to
+    // run the translation chain a few hundred instructions after the rotation chain -- fetching every entry of every Rc twice
+    // (arm7: 338 v_accvgpr_read per iteration instead of 220).  Pinning p and one entry of R after each joint keeps the two together.
+    // Not for the structural chains: their table stays in vector registers, and a pin keeps a literal entry from folding.
+    constexpr bool kPinWalk = S::offset(NJ + 1) > kHotTableVgprMax;
+    // joint J: its local column from Y (the same before and after the joint's own rotation), then Y <- P_J Rz(q_J) Y
+#define IKD_HOT_JOINT(J)                                                                                   \
+    if (J < NJ) {                                                                                          \
+        constexpr int jj = J < NJ ? J : 0;                                                                 \
+        ang[jj][0] = R[6]; ang[jj][1] = R[7]; ang[jj][2] = R[8];                                           \
+        lin[jj][0] = dfma(p[0], R[3], -(p[1] * R[0]));                                                     \
+        lin[jj][1] = dfma(p[0], R[4], -(p[1] * R[1]));                                                     \
+        lin[jj][2] = dfma(p[0], R[5], -(p[1] * R[2]));                                                     \
+        rot_z_left(R, p, sn[jj], cs[jj]);                                                                  \
+        hot_compose_left<S, jj>(R, p, t);                                                                  \
+        if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }                      \
+    }
+    IKD_HOT_JOINT(6) IKD_HOT_JOINT(5) IKD_HOT_JOINT(4) IKD_HOT_JOINT(3) IKD_HOT_JOINT(2) IKD_HOT_JOINT(1) IKD_HOT_JOINT(0)
+#undef IKD_HOT_JOINT
+
+    // (R, p) = oMf;  fMt = oMf^-1 oMt
     double Re[9], pe[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -156,31 +190,19 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
 #pragma unroll
     for (int i = 0; i < 6; ++i) e[i] = lj.e[i];
 
-    // K' = Jlog6(tMf) with the frame rotation folded in: top rows [A Rf^T | Bm Rf^T], bottom rows [0 | A Rf^T]
-    double AR[9], BR[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            AR[3 * i + k] = dfma(lj.A[3 * i], R[3 * k], dfma(lj.A[3 * i + 1], R[3 * k + 1], lj.A[3 * i + 2] * R[3 * k + 2]));
-        }
-    // (C A) Rf^T = C (A Rf^T): the product C A itself is never formed
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            BR[3 * i + k] = dfma(Cm[3 * i], AR[k], dfma(Cm[3 * i + 1], AR[3 + k], Cm[3 * i + 2] * AR[6 + k]));
+    // Jlog6(tMf) = [A  C A; 0  A] on the local columns [lin_j; ang_j]:  beta_j = A ang_j (shared by a run of parallel joints),
+    // top = A lin_j + C beta_j.  The product C A is never formed.
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        const double dj[3] = {org[j][0] - p[0], org[j][1] - p[1], org[j][2] - p[2]};
-        double vw[3];
-        cross(dj, zax[j], vw);
+        double beta[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) beta[i] = dfma(lj.A[3 * i], ang[j][0], dfma(lj.A[3 * i + 1], ang[j][1], lj.A[3 * i + 2] * ang[j][2]));
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            // the z-axis terms first: consecutive joints with parallel axes (identity-rotation placements) share them
-            const double bz = dfma(BR[3 * i], zax[j][0], dfma(BR[3 * i + 1], zax[j][1], BR[3 * i + 2] * zax[j][2]));
-            col[j][i] = dfma(AR[3 * i], vw[0], dfma(AR[3 * i + 1], vw[1], dfma(AR[3 * i + 2], vw[2], bz)));
-            col[j][3 + i] = dfma(AR[3 * i], zax[j][0], dfma(AR[3 * i + 1], zax[j][1], AR[3 * i + 2] * zax[j][2]));
+            // the beta terms first: consecutive joints with parallel axes share them
+            const double cb = dfma(Cm[3 * i], beta[0], dfma(Cm[3 * i + 1], beta[1], Cm[3 * i + 2] * beta[2]));
+            col[j][i] = dfma(lj.A[3 * i], lin[j][0], dfma(lj.A[3 * i + 1], lin[j][1], dfma(lj.A[3 * i + 2], lin[j][2], cb)));
+            col[j][3 + i] = beta[i];
         }
     }
 }
@@ -190,8 +212,8 @@ template <int NJ, class S>
 IKD_FN void hot_gram(const double (&col)[NJ][6], double lam2, double (&G)[36]) {
     constexpr int M = 6;
     constexpr typename ChainRuns<S, NJ>::Table kRuns = ChainRuns<S, NJ>::value;
-            // Gram matrix.  Joints of one run of parallel axes (S::leader) share their bottom (angular) rows: col[j][3..5] = A Rf^T z_j is
-            // the same vector for all of them, so  sum_j col[j][3+a] col[j][3+b] = n c_a c_b  and  sum_j col[j][3+a] col[j][b] =
+            // Gram matrix.  Joints of one run of parallel axes (S::leader) share their bottom (angular) rows: col[j][3..5] = A ang_j is
+            // the same vector for all of them (hot_evaluate's invariant), so  sum_j col[j][3+a] col[j][3+b] = n c_a c_b  and  sum_j col[j][3+a] col[j][b] =
             // c_a (sum_j col[j][b])  within a run -- 102 instead of 147 multiply-adds for a Cassie leg (runs of 1, 1 and 5 joints).
                     double top_sum[NJ][3], nbot[NJ][3];
     #pragma unroll
@@ -514,8 +536,8 @@ IKD_FN void hot_solutions_body(const ChainKernelArgs<NJ> &a, const SolutionsArgs
 #define IKGPU_HOT_PIN_HI (S::offset(NJ + 1))
 #endif
 
-// The compact table (<= 36 doubles for the fixture shapes) arrives in the kernel-argument segment and is parked in vector
-// registers for the whole loop: in scalar registers it competes with the ~40 polynomial constants for the 100 SGPRs (31 v_readlane
+// The compact table (<= 36 doubles for the fixture shapes, see kHotTableVgprMax) arrives in the kernel-argument segment and is parked
+// in vector registers for the whole loop: in scalar registers it competes with the ~40 polynomial constants for the 100 SGPRs (31 v_readlane
 // + 39 s_mov of spill code per iteration in the round-1 kernel); a lone wave has 512 VGPRs to itself.
 template <int NJ, class S>
 __device__ __forceinline__ void hot_park_table(const HotTable &t, HotTable &tv) {

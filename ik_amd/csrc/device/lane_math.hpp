@@ -351,6 +351,19 @@ IKD_FN void rot_z_right(double (&R)[9], double s, double c) {
     }
 }
 
+// (R, p) <- Rz(angle) * (R, p) given (sin, cos): rows 0 and 1 of R and p[0], p[1] mix; row 2 and p[2] are not touched
+IKD_FN void rot_z_left(double (&R)[9], double (&p)[3], double s, double c) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double a = R[k], b = R[3 + k];
+        R[k] = dfma(a, c, -(b * s));
+        R[3 + k] = dfma(b, c, a * s);
+    }
+    const double a = p[0], b = p[1];
+    p[0] = dfma(a, c, -(b * s));
+    p[1] = dfma(b, c, a * s);
+}
+
 // out = R^T v
 IKD_FN void rotT_vec(const double (&R)[9], const double (&v)[3], double (&out)[3]) {
 #pragma unroll

@@ -25,4 +25,4 @@ for k in ("k_sincos", "k_evaluate", "k_gram", "k_chol", "k_step"):
     if k != "k_sincos":
         total += len(f64)
     print("%-11s %4d FP64 instructions  %s" % (k[2:], len(f64), dict(collections.Counter(f64).most_common(5))))
-print("evaluate + gram + chol + step = %d (the loop executes 1 052 VALU instructions per wave-iteration: PMC, DESIGN.md section 3.1)" % total)
+print("evaluate + gram + chol + step = %d (the loop's executed VALU instructions per wave-iteration, from the counters: DESIGN.md section 3.1)" % total)

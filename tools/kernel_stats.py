@@ -99,7 +99,12 @@ def main():
                     for kk, vv in sub.items():
                         c[kk] += vv * trips
             return c
-        main = max(tops, key=lambda h: sum(per_header[h].values()) + sum(sum(per_header[k].values()) for k in per_header if depth_of.get(k, 1) > 1))
+        # (by FP64 instructions, then by size: the hot chain kernels' pass-through loop -- loads, stores, address arithmetic -- is as long
+        # as the 6-joint iteration loop)
+        def f64(h):
+            return sum(v for k, v in per_header[h].items() if k.endswith("_f64"))
+        main = max(tops, key=lambda h: (f64(h) + sum(f64(k) for k in per_header if depth_of.get(k, 1) > 1),
+                                        sum(per_header[h].values()) + sum(sum(per_header[k].values()) for k in per_header if depth_of.get(k, 1) > 1)))
         c = total(main)
         meta = text[text.index(name, text.index(".amdhsa_kernel")):]
         def grab(key):
