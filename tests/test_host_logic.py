@@ -212,6 +212,13 @@ def test_plan_names_the_kernel_for_the_benchmark_shapes(ik):
     assert ik.plan(_problem(ik, "ur5", ["tool0"])[1]) == "dls_chain<NJ=6,full,hot>"
     assert ik.plan(_problem(ik, "cassie_fixed", ["RightFootFront"], types=[ik.KinematicType.Position])[1]) == "dls_chain<NJ=7,position,general>"
     assert ik.plan(_problem(ik, "ur5", ["wrist_1_link"], types=[ik.KinematicType.Orientation])[1]) == "dls_chain<NJ=4,orientation,general>"
+    # ... and every chain length the general kernel is instantiated for: l1 .. l7 and tool of arm8 (tests/chain_shapes_common.py)
+    import chain_shapes_common as CS
+    arm8 = ik.Model.from_urdf_xml(CS.arm8_xml())
+    for nj, frame in enumerate(CS.ARM_FRAMES, 1):
+        p = ik.InverseKinematicsProblem(arm8)
+        p.add_frame_task("t", ik.FrameTask.create(arm8, frame, ik.KinematicType.Orientation))
+        assert ik.plan(p) == "dls_chain<NJ=%d,orientation,general>" % nj
     assert ik.plan(_problem(ik, "arm7", ["tool"])[1]) in ("dls_chain<NJ=7,full,hot-rtc>", "dls_chain<NJ=7,full,general>")   # (general when libhiprtc is absent)
 
 
