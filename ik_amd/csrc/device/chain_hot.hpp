@@ -72,15 +72,34 @@ struct ChainStruct {
     static constexpr int members(int L, int nj) { return nj <= 0 ? 0 : members(L, nj - 1) + (leader(nj - 1) == L ? 1 : 0); }
 };
 
+// The shortest run of parallel joints that hot_evaluate walks in the run's own frame ("folds").  From the static counts of the
+// iteration loop (v_mov_b64 two issue slots, a transcendental four): each member after the first saves the 16
+// instructions that rotate rows 0, 1 of R and p, and pays one addition for its angle sum and one extra multiply-add per in-plane
+// translation component; forming lin_j and A lin_j costs 6 + 9 = 15 per member unfolded against 6 per member and 18 once per run
+// folded (A r0, A r1), which is even at two joints (30 = 30) and ahead from three.  A run of two therefore already pays, and the
+// listing agrees: UR5 / UR10 (one run of two) 1049 -> 1035 slots with no copy added and ten registers fewer.  A run of one has
+// nothing to fold; 1 here would only send every joint down the folded path for no gain.
+// Known cost: in a chain whose table is parked in accumulation registers (kHotTableVgprMax) the allocator spills around the
+// theta -> pi arm of log3 once a run is folded -- the all-general 7-joint chain with a run of three: executed path 1419 -> 1356 slots,
+// that arm 116 -> 251 -- so a wave of such a chain that enters the arm (a lane within 1e-2 of pi) pays more than before.
+constexpr int kHotFoldMinRun = 2;
+
 // leader / members as compile-time tables (indexed by the unrolled joint loops: a constant index into a constant array folds;
 // the recursive constexpr functions above, called with a loop variable, would be emitted as real calls)
+// folded[j]: joint j's run is walked in the run's own frame by hot_evaluate (a run of at least kHotFoldMinRun joints); tip[j]: j is
+// the tip-side end of its run (the member the tip-to-base walk meets first); any_folded: the chain has a folded run.
 template <class S, int NJ>
 struct ChainRuns {
-    struct Table { int leader[8], members[8]; };
+    struct Table { int leader[8], members[8]; bool folded[8], tip[8], any_folded; };
     static constexpr Table make() {
         Table t{};
         for (int j = 0; j < 8; ++j) { t.leader[j] = j < NJ ? S::leader(j) : j; t.members[j] = 0; }
         for (int j = 0; j < NJ; ++j) ++t.members[t.leader[j]];
+        for (int j = 0; j < 8; ++j) {
+            t.folded[j] = t.members[t.leader[j]] >= kHotFoldMinRun;
+            t.tip[j] = j == t.leader[j] + t.members[t.leader[j]] - 1;
+            if (j < NJ && t.folded[j]) t.any_folded = true;
+        }
         return t;
     }
     static constexpr Table value = make();
@@ -138,14 +157,37 @@ IKD_FN void hot_compose_left(double (&R)[9], double (&p)[3], const Tab &t) {
 // INVARIANT hot_gram and hot_step rely on: inside a run of identity-rotation placements (S::leader) the angular parts ang[j], and so
 // col[j][3..5], are the SAME values for every member -- rot_z_left leaves row 2 of R alone and an identity Rc folds away in
 // hot_compose_left, so the members read the same registers.
+// FOLDED RUNS (ChainRuns::folded, runs of at least kHotFoldMinRun joints).  Between the members of a run the placements are pure
+// translations, so the walk stays in the frame it entered the run with and Y is materialised once, at the run's leader:
+//  * rows 0 and 1 of R at the run's entry, r0 and r1, serve every member the way row 2 does -- R is simply not touched until the
+//    leader; ang[j] is still row 2 of R, the very same registers for every member, and the invariant above holds unchanged;
+//  * the running translation is kept in the entry frame, p~ = Rz(-phi_j) p with phi_j the SUM of the run's angles from its tip-side
+//    member down to j, and is what differs from member to member:  lin_j = R^T (e_z x p) = p~0 r1 - p~1 r0;  joint j's own rotation
+//    leaves p~ alone and its translation enters as p~ += Rz(-phi_j) t_j -- two multiply-adds per non-zero in-plane component, one
+//    addition along the axis; a member without in-plane translation needs no sin / cos at all;
+//  * A lin_j = p~0 (A r1) - p~1 (A r0): the two products are formed once per run and lin_j itself never;
+//  * at the leader (R, p) <- P_L Rz(phi_L) (R, p~): the same rot_z_left and hot_compose_left as for a lone joint.
+// The step, the joint limits and q stay per joint (hot_step); only sin and cos take phi_j.  Argument of dsincos_hot: its one-word
+// reduction by 2 pi leaves an error of 3.9e-17 |x|.  Every joint of a chain problem is a bounded revolute (continuous joints go to
+// the generic kernel) and q is clipped to its limits after every step, so from the second evaluation on |phi_j| <= the sum of the
+// run's max(|lo|, |hi|).  Nothing bounds a URDF's limits (or the caller's q0, which the first evaluation sees unclipped), so this is
+// no guarantee, only the scale of the error: under the ASSUMPTION of at most a full turn either way per joint a whole chain of seven
+// reaches 44 rad and 1.7e-15, below the 2e-15 of the kernels, which holds up to |phi| = 51 rad; limits of +-100 rad on a run of seven
+// give |phi| = 700 and 2.7e-14.  The folded form's error thus grows with the run's SUM where the unfolded one grew with each joint's own
+// angle.  The second word of 2 pi (dsincos_fast) would not change that: phi_j is a rounded sum, each of its additions is off by up to
+// half an ulp of |phi| (5.5e-17 .. 1.1e-16 |phi|), more than the dropped word's 3.9e-17 |phi|.  So the one-word reduction stays.
 template <int NJ, class S, class Tab>
 IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt)[12], double (&e)[6], double (&col)[NJ][6]) {
-    // the NJ sin / cos first: independent of the chain, the constants are live once
-    double sn[NJ], cs[NJ];
+    constexpr typename ChainRuns<S, NJ>::Table kRuns = ChainRuns<S, NJ>::value;
+    // the NJ sin / cos first: independent of the chain, the constants are live once.  A member of a folded run takes phi_j.
+    double phi[NJ], sn[NJ], cs[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) dsincos_hot(q[j], sn[j], cs[j]);
+    for (int j = NJ - 1; j >= 0; --j) phi[j] = (kRuns.folded[j] && !kRuns.tip[j]) ? phi[j + 1 < NJ ? j + 1 : j] + q[j] : q[j];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) dsincos_hot(phi[j], sn[j], cs[j]);
 
     double ang[NJ][3], lin[NJ][3];
+    double rows[NJ][6], pt[NJ][2];   // folded runs: rows 0 and 1 of R at the run's entry (by leader), p~0 and p~1 (by member)
     double R[9], p[3];
     // placement NJ: last joint frame -> task frame
 #pragma unroll
@@ -164,16 +206,46 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
     if (J < NJ) {                                                                                          \
         constexpr int jj = J < NJ ? J : 0;                                                                 \
         ang[jj][0] = R[6]; ang[jj][1] = R[7]; ang[jj][2] = R[8];                                           \
-        lin[jj][0] = dfma(p[0], R[3], -(p[1] * R[0]));                                                     \
-        lin[jj][1] = dfma(p[0], R[4], -(p[1] * R[1]));                                                     \
-        lin[jj][2] = dfma(p[0], R[5], -(p[1] * R[2]));                                                     \
-        rot_z_left(R, p, sn[jj], cs[jj]);                                                                  \
-        hot_compose_left<S, jj>(R, p, t);                                                                  \
-        if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }                      \
+        if (!kRuns.folded[jj]) {                                                                           \
+            lin[jj][0] = dfma(p[0], R[3], -(p[1] * R[0]));                                                 \
+            lin[jj][1] = dfma(p[0], R[4], -(p[1] * R[1]));                                                 \
+            lin[jj][2] = dfma(p[0], R[5], -(p[1] * R[2]));                                                 \
+            rot_z_left(R, p, sn[jj], cs[jj]);                                                              \
+            hot_compose_left<S, jj>(R, p, t);                                                              \
+            if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }                  \
+        } else {                                                                                           \
+            /* (R, p) = (R at the run's entry, p~): A lin_j = p~0 (A r1) - p~1 (A r0) once A is known */   \
+            pt[jj][0] = p[0]; pt[jj][1] = p[1];                                                            \
+            if (kRuns.leader[jj] != jj) {                                                                  \
+                /* p~ += Rz(-phi_j) t_j: the member's placement is a pure translation */                   \
+                if (S::tnz(jj, 0)) {                                                                       \
+                    const double t0 = t.v[S::trans_at(jj, 0)];                                             \
+                    p[0] = dfma(cs[jj], t0, p[0]); p[1] = dfma(-sn[jj], t0, p[1]);                         \
+                }                                                                                          \
+                if (S::tnz(jj, 1)) {                                                                       \
+                    const double t1 = t.v[S::trans_at(jj, 1)];                                             \
+                    p[0] = dfma(sn[jj], t1, p[0]); p[1] = dfma(cs[jj], t1, p[1]);                          \
+                }                                                                                          \
+                if (S::tnz(jj, 2)) p[2] += t.v[S::trans_at(jj, 2)];                                        \
+            } else {                                                                                       \
+                /* the leader: Y is materialised, (R, p) <- P_L Rz(phi_L) (R, p~) */                       \
+                _Pragma("unroll") for (int k = 0; k < 6; ++k) rows[jj][k] = R[k];                          \
+                rot_z_left(R, p, sn[jj], cs[jj]);                                                          \
+                hot_compose_left<S, jj>(R, p, t);                                                          \
+                if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }              \
+            }                                                                                              \
+        }                                                                                                  \
     }
     IKD_HOT_JOINT(6) IKD_HOT_JOINT(5) IKD_HOT_JOINT(4) IKD_HOT_JOINT(3) IKD_HOT_JOINT(2) IKD_HOT_JOINT(1) IKD_HOT_JOINT(0)
 #undef IKD_HOT_JOINT
 
+    // In a folded run R does not depend on the members' own sin / cos -- only p~ does -- and the compiler was seen to sink those past
+    // the branch inside log6, away from the others: the two polynomial constants that each sin / cos takes through a vector register
+    // (v_mov_b64, 8 cycles of issue each) were then copied twice per iteration (Cassie leg: 5 v_mov_b64 in the loop, with the pin 3,
+    // the unfolded loop's own; the leader's rows[][] = R[] is a copy in the source only: R is not written inside a run, and the
+    // built kernels hold r0, r1 in the registers R had -- a fact of the listings, tools/kernel_stats.py, not of the source).  A folded member needs no kPinWalk pin: it has no rotation chain for p to drift away from (the
+    // all-general 7-joint chain with three of its placements made identity: the same listing with and without).
+    if (kRuns.any_folded) { IKD_PIN(p[0]); IKD_PIN(p[1]); }
     // (R, p) = oMf;  fMt = oMf^-1 oMt
     double Re[9], pe[3];
 #pragma unroll
@@ -190,8 +262,20 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
 #pragma unroll
     for (int i = 0; i < 6; ++i) e[i] = lj.e[i];
 
+    // folded runs: A r0 and A r1, once per run
+    double Ar0[NJ][3], Ar1[NJ][3];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        if (kRuns.folded[j] && kRuns.leader[j] == j) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                Ar0[j][i] = dfma(lj.A[3 * i], rows[j][0], dfma(lj.A[3 * i + 1], rows[j][1], lj.A[3 * i + 2] * rows[j][2]));
+                Ar1[j][i] = dfma(lj.A[3 * i], rows[j][3], dfma(lj.A[3 * i + 1], rows[j][4], lj.A[3 * i + 2] * rows[j][5]));
+            }
+        }
+
     // Jlog6(tMf) = [A  C A; 0  A] on the local columns [lin_j; ang_j]:  beta_j = A ang_j (shared by a run of parallel joints),
-    // top = A lin_j + C beta_j.  The product C A is never formed.
+    // top = A lin_j + C beta_j.  The product C A is never formed.  In a folded run A lin_j = p~0 (A r1) - p~1 (A r0).
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         double beta[3];
@@ -201,7 +285,10 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
         for (int i = 0; i < 3; ++i) {
             // the beta terms first: consecutive joints with parallel axes share them
             const double cb = dfma(Cm[3 * i], beta[0], dfma(Cm[3 * i + 1], beta[1], Cm[3 * i + 2] * beta[2]));
+            if (!kRuns.folded[j])
             col[j][i] = dfma(lj.A[3 * i], lin[j][0], dfma(lj.A[3 * i + 1], lin[j][1], dfma(lj.A[3 * i + 2], lin[j][2], cb)));
+            else
+                col[j][i] = dfma(pt[j][0], Ar1[kRuns.leader[j]][i], dfma(-pt[j][1], Ar0[kRuns.leader[j]][i], cb));
             col[j][3 + i] = beta[i];
         }
     }

@@ -7,6 +7,11 @@ conversions = 1 -- per lane; the count is of *executed* instructions (what the h
 not of an algorithmic minimum.  Both sides of wave-uniform branches are counted, so these static_* numbers are upper
 bounds; the flop count bench.py uses is the measured one (tools/pmc_to_stats.py).  Merges into ik_amd/kernel_stats.json.
 
+Issue slots (static_loop_issue_slots): what a lone wave pays for the loop, in units of 4 cycles -- every instruction one slot,
+v_mov_b64 two, an FP64 transcendental (v_rcp / v_rsq / v_sqrt) four (tools/issue_probe.hip, profiles/r02_issue_probe.csv).
+static_loop_blocks lists the loop's basic blocks in order with their instructions and slots: in the chain kernels the last one is
+the theta -> pi arm of log3, entered only when some lane of the wave is within 1e-2 of pi.
+
     python tools/kernel_stats.py
 """
 import collections
@@ -23,7 +28,18 @@ KERNELS = {  # display name -> (source file, extra flags, mangled-name fragment,
     "dls_chain<NJ=7,full>": ("kernels_hot.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "dls_chain_hot_kernelILi7E", 1),
     "dls_chain<NJ=6,full>": ("kernels_hot.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "dls_chain_hot_kernelILi6E", 1),
     "dls_tree<NJ=7,chains=2,base_task>": ("kernels.hip", [], "dls_tree_kernelILi7ELi2E", 2),
+    # structure codes compiled at run time, as stand-ins built offline (tools/hot_rtc_shapes.hip: the all-general 7-joint chain, and the same
+    # with a run of three); keys of their own: 'dls_chain<NJ=7,full,hot-rtc>' holds the counters of the real arm7 kernel hipRTC builds
+    "dls_chain<NJ=7,full,hot-rtc>|all-general stand-in": ("../../tools/hot_rtc_shapes.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "hot_rtc_shape_kernelILi7ELm8070454380540461056ELm8070454380540461056E", 1),
+    "dls_chain<NJ=7,full,hot-rtc>|all-general stand-in with a run of three": ("../../tools/hot_rtc_shapes.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "hot_rtc_shape_kernelILi7ELm8070454380540461056ELm8744121078061465600E", 1),
 }
+TRANSCENDENTAL = ("v_rcp_f64", "v_rsq_f64", "v_sqrt_f64")
+
+
+def issue_slots(c):
+    return sum(c.values()) + c["v_mov_b64"] + 3 * sum(c[k] for k in TRANSCENDENTAL)
+
+
 FLOPS = {"v_fma_f64": 2, "v_fmac_f64": 2, "v_mul_f64": 1, "v_add_f64": 1, "v_min_f64": 1, "v_max_f64": 1,
          "v_rcp_f64": 1, "v_rsq_f64": 1, "v_rndne_f64": 1, "v_ldexp_f64": 1, "v_cvt_i32_f64": 1, "v_cvt_f64_i32": 1,
          "v_sqrt_f64": 1, "v_fract_f64": 1, "v_trig_preop_f64": 1, "v_div_scale_f64": 1, "v_div_fmas_f64": 2,
@@ -34,7 +50,7 @@ def main():
     texts = {}
     with tempfile.TemporaryDirectory() as td:
         for src, flags in {(v[0], tuple(v[1])) for v in KERNELS.values()}:
-            asm = os.path.join(td, src + ".s")
+            asm = os.path.join(td, os.path.basename(src) + ".s")
             cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
                    "-I" + os.path.join(ROOT, "ik_amd", "csrc"), "--offload-arch=gfx950", "-fno-fast-math", "-ffp-contract=" + os.environ.get("IKGPU_FP_CONTRACT", "on"),
                    *flags, "-S", "--cuda-device-only", os.path.join(ROOT, "ik_amd", "csrc", src), "-o", asm]
@@ -106,6 +122,20 @@ def main():
         main = max(tops, key=lambda h: (f64(h) + sum(f64(k) for k in per_header if depth_of.get(k, 1) > 1),
                                         sum(per_header[h].values()) + sum(sum(per_header[k].values()) for k in per_header if depth_of.get(k, 1) > 1)))
         c = total(main)
+        # the loop's own basic blocks in listing order (labelled blocks and the fall-through "; %bb.N" ones)
+        blocks, at = [], None
+        for l in body:
+            t = l.strip()
+            mlab = re.match(r"^\.?L?(BB\d+_\d+):", t)
+            if mlab or t.startswith("; %bb."):
+                inside = (mlab is not None and mlab.group(1) == main) or ("Header=%s " % main) in t
+                at = collections.Counter() if inside else None
+                if inside:
+                    blocks.append(at)
+                continue
+            if at is None or not t or t.startswith((".", ";", "//")):
+                continue
+            at[re.sub(r"_e(32|64)$", "", t.split()[0])] += 1
         meta = text[text.index(name, text.index(".amdhsa_kernel")):]
         def grab(key):
             mm = re.search(r"%s\s+(\d+)" % key, meta)
@@ -117,6 +147,12 @@ def main():
             "fp64_fma_instructions": c["v_fma_f64"] + c["v_fmac_f64"],
             "flop_per_iteration": flops,
             "lds_reads": sum(v for k, v in c.items() if k.startswith("ds_read")),
+            "loop_issue_slots": issue_slots(c),
+            "loop_blocks": [{"instructions": sum(b.values()), "issue_slots": issue_slots(b)} for b in blocks] if len(blocks) <= 8 else None,
+            "loop_v_mov_b64": c["v_mov_b64"],
+            "loop_v_accvgpr_read": c["v_accvgpr_read_b32"],
+            "loop_v_accvgpr_write": c["v_accvgpr_write_b32"],
+            "scratch_bytes": grab(r"\.amdhsa_private_segment_fixed_size"),
             "next_free_vgpr": grab(r"\.amdhsa_next_free_vgpr"),
             "accum_offset": grab(r"\.amdhsa_accum_offset"),
             "top_instructions": dict(c.most_common(12)),
@@ -128,7 +164,8 @@ def main():
     for k, v in out.items():  # keep what tools/pmc_to_stats.py measured (traffic, flop counts, raw counters)
         merged = dict(old.get(k, {}))
         merged.update({"static_" + kk if kk in ("flop_per_iteration", "loop_instructions", "fp64_valu_instructions",
-                                                  "fp64_fma_instructions", "lds_reads", "top_instructions") else kk: vv
+                                                  "fp64_fma_instructions", "lds_reads", "top_instructions", "loop_issue_slots", "loop_blocks",
+                                                  "loop_v_mov_b64", "loop_v_accvgpr_read", "loop_v_accvgpr_write") else kk: vv
                        for kk, vv in v.items()})
         out[k] = merged
     for k, v in old.items():
