@@ -10,10 +10,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ikgpu.h"
@@ -21,16 +23,37 @@
 #include "model.hpp"
 #include "problem.hpp"
 
-// Staging area of the host-pointer entry points for small batches (host_solve below): grows on demand, guarded by a mutex a
+namespace {
+
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
+        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// Staging area of the host-pointer entry points for small batches (solve_staged below): grows on demand, guarded by a mutex a
 // caller only ever try-locks.
 struct Staging {
     std::mutex mu;
     void *dev = nullptr, *host = nullptr;
     size_t cap = 0;
+    void release() {
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        dev = host = nullptr;
+        cap = 0;
+    }
+    ~Staging() { release(); }
 };
 constexpr size_t kStageLimit = size_t(1) << 20;  // batches whose buffers total at most 1 MiB take the staged path
 
-// Per-phase wall clock of the pipelined host entry (host_solve below), switched on by IKGPU_HOST_TRACE=<file>: one line per call --
+// Per-phase wall clock of the pipelined host entry (solve_pipelined below), switched on by IKGPU_HOST_TRACE=<file>: one line per call --
 // total and the time spent waiting for the pipe's mutex, in set-up, enqueueing copies and launches, and in each of the final waits.
 // (Round 3 saw 30-75 ms stalls about once per hundred calls: this is how the phase that carries them is found;
 // tools/host_entry_tails.py reads the file.)
@@ -59,7 +82,22 @@ struct HostPipe {
     hipStream_t in = nullptr, out = nullptr;
     hipStream_t run[kRunStreams] = {};   // chunk k solves on run[k % 8]
     std::vector<hipEvent_t> ev_in, ev_run;
+    void release() {
+        if (dev) (void)hipFree(dev);
+        dev = nullptr;
+        cap = 0;
+        for (hipEvent_t ev : ev_in) (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : ev_run) (void)hipEventDestroy(ev);
+        ev_in.clear();
+        ev_run.clear();
+        if (in) { (void)hipStreamDestroy(in); (void)hipStreamDestroy(out); }
+        in = out = nullptr;
+        for (hipStream_t &r : run) { if (r) (void)hipStreamDestroy(r); r = nullptr; }
+    }
+    ~HostPipe() { release(); }
 };
+
+}  // namespace
 
 struct ikgpu_problem {
     mutable Staging stage;
@@ -85,12 +123,25 @@ struct ikgpu_problem {
     mutable std::once_flag pik_static_once[2];
     mutable uint64_t pik_static_key[2] = {0, 0};
     mutable bool pik_static[2] = {false, false};
-    mutable std::string pik_static_name;
     std::vector<uint8_t> draw;   // [nq] entries a generated start of a multi-start solve draws (problem.hpp multistart_draw_mask)
     std::string dls_name;    // what ikgpu_problem_kernel reports
     std::string pik_name;    // name of the generic PIK kernel instance
     std::string pik_tree_name;  // ... and of the tree kernel running a two-level ik::pik (when the problem has that shape)
+    std::string pik_static_name;  // ... and of the compiled lane program (formed at creation: ikgpu_pik_kernel only reads)
+    explicit ikgpu_problem(int device_) : device(device_) {}
+    ~ikgpu_problem() {   // everything the problem holds on its device, released on that device
+        DeviceGuard g(device);
+        void *const tables[] = {dev.lower, dev.upper, dev.q_in_chain, dev.draw, dev.chain_desc, dev.g_ints, dev.g_dbls};
+        for (void *t : tables) (void)hipFree(t);
+        dev.queues.release();
+        pipe.release();    // (here, not in the members' own destructors: those run after the guard has gone)
+        stage.release();
+    }
 };
+// (each of them owns device memory: a copy would free it twice)
+static_assert(!std::is_copy_constructible<Staging>::value && !std::is_copy_constructible<HostPipe>::value &&
+                  !std::is_copy_constructible<ikgpu_problem>::value && !std::is_copy_assignable<ikgpu_problem>::value,
+              "owners of device memory must not be copyable");
 
 namespace {
 
@@ -104,8 +155,8 @@ bool shape_built(const ikgpu::ProblemHost &ph) {
 
 // Analysis + the "is this specialisation compiled" check; a specialised shape without an instantiation
 // falls back to the generic kernel.  Throws std::runtime_error on invalid input.
-ikgpu::ProblemHost analyse(const ikgpu::Model &m, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *cons = nullptr,
-                           int32_t ncons = 0, bool compile_rtc = false) {
+ikgpu::ProblemHost analyse(const ikgpu::Model &m, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *cons, int32_t ncons,
+                           bool compile_rtc) {
     // IKGPU_DLS_KERNEL=generic skips the register-resident specialisations (the parity tests compare them with the generic kernel)
     const char *force = std::getenv("IKGPU_DLS_KERNEL");
     ikgpu::ProblemHost ph = ikgpu::analyse_problem(m, tasks, ntasks, force && std::strcmp(force, "generic") == 0, cons, ncons);
@@ -145,6 +196,28 @@ std::string static_name(const ikgpu::ProblemHost &gen) {
     return n.size() > 8 && n.compare(n.size() - 8, 8, ",static>") == 0 ? n : n.substr(0, n.size() - 1) + ",static>";
 }
 
+// Which kernel ik::dls runs a problem on: what ikgpu_problem_create builds (compile = true: the run-time compiled builds are
+// compiled, first the one `analyse` picks, then the Tree problem's static program) and what ikgpu_problem_plan names without
+// compiling anything (compile = false).  Throws std::runtime_error on invalid input.
+struct KernelPlan {
+    ikgpu::ProblemHost host, gen;   // the problem's own analysis; the same problem analysed for the generic lane program
+    bool dls_on_static_gen = false;
+    std::string name;               // what ikgpu_problem_kernel reports
+};
+KernelPlan plan_kernels(const ikgpu::Model &m, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *cons, int32_t ncons, bool compile) {
+    KernelPlan k;
+    k.host = analyse(m, tasks, ntasks, cons, ncons, compile);
+    // (for a Generic problem `analyse` has compiled the static program: gen is a copy of host, build and key included)
+    k.gen = k.host.kind == ikgpu::KernelKind::Generic ? k.host : ikgpu::analyse_problem(m, tasks, ntasks, /*force_generic=*/true, cons, ncons);
+    k.name = k.host.kernel_name;
+    if (tree_prefers_static(k.host) && ikgpu::rtc_generic_static_available(k.gen, compile, &k.gen.generic_key)) {
+        k.gen.generic_build = 2;
+        k.dls_on_static_gen = true;
+        k.name = static_name(k.gen);
+    }
+    return k;
+}
+
 }  // namespace
 
 // (shard.cpp reports through the same thread-local message)
@@ -155,6 +228,9 @@ namespace {
 int hip_fail(hipError_t e, const char *what) {
     return fail(IKGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// What a launcher returned, as the entry point's return code.
+int launched(hipError_t e, const char *what) { return e == hipSuccess ? static_cast<int>(IKGPU_OK) : hip_fail(e, what); }
 
 template <class F>
 int guarded(F &&f) {
@@ -169,32 +245,60 @@ int guarded(F &&f) {
     }
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+// The scope every entry point launches in: `device` selected (and the caller's restored on the way out), no exception past the
+// boundary (the launchers throw for a shape without an instantiation).  body(stream) returns the entry point's return code.
+template <class F>
+int on_device(int device, void *stream, F &&body) {
+    return guarded([&] {
+        DeviceGuard g(device);
+        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
+        return static_cast<int>(body(static_cast<hipStream_t>(stream)));
+    });
+}
+
+// The refusals of the entry points, each rule once; an entry point composes them in its own order (which is part of its contract:
+// tests/test_capi_refusals_host.py).  Only check_pik_params reads the problem, after its own null tests: any other refusal, and the
+// empty-batch no-op, never look at the handle.
+int refuse_if(bool bad, const char *msg) { return bad ? fail(IKGPU_ERR_INVALID, msg) : IKGPU_OK; }
+
+int null_argument() { return refuse_if(true, "null argument"); }
+
+int check_batch(int64_t B) { return refuse_if(B < 0, "negative batch size"); }
+
+int check_problem(const ikgpu_problem *p) { return refuse_if(!p, "null problem"); }
+
+int check_problem_batch(const ikgpu_problem *p, int64_t B) {
+    if (int rc = check_problem(p)) return rc;
+    return check_batch(B);
+}
+
+int check_layout(int layout) { return refuse_if(layout != IKGPU_SOA && layout != IKGPU_AOS, "unknown layout"); }
+
+// ... of a host-pointer entry, where targets may arrive as 7 doubles per task (IKGPU_TARGETS_POSE7)
+int check_host_layout(int layout) { return check_layout(layout & ~IKGPU_TARGETS_POSE7); }
+
+int check_starts(int32_t K) { return refuse_if(K < 1 || K > 64, "the number of starts must be 1 .. 64"); }
+
+// one launch takes B x K lanes (K starts per problem, 1 <= K)
+int check_launch_size(int64_t B, int32_t K = 1) { return refuse_if(B > (int64_t(1) << 31) * 32 / K, "batch too large for one launch"); }
+
+int check_have_params(const void *prm) { return refuse_if(!prm, "params is null"); }
+
+int check_max_iterations(int32_t n) { return refuse_if(n < 0, "max_iterations must be >= 0"); }
 
 int check_params(const ikgpu_dls_params *p) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "params is null");
-    if (p->max_iterations < 0) return fail(IKGPU_ERR_INVALID, "max_iterations must be >= 0");
-    if (!(p->damping > 0.0))
-        return fail(IKGPU_ERR_INVALID, "damping must be > 0: the device solves JJ^T + damping^2 I by Cholesky (SPD)");
+    if (int rc = check_have_params(p)) return rc;
+    if (int rc = check_max_iterations(p->max_iterations)) return rc;
+    if (int rc = refuse_if(!(p->damping > 0.0), "damping must be > 0: the device solves JJ^T + damping^2 I by Cholesky (SPD)")) return rc;
     if (p->num_level_tols < 0 || p->num_level_tols > IKGPU_MAX_VISITOR_LEVELS)
         return fail(IKGPU_ERR_INVALID, "num_level_tols must be in 0.." + std::to_string(IKGPU_MAX_VISITOR_LEVELS));
     return IKGPU_OK;
 }
 
 int check_pik_params(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
-    if (!prm) return fail(IKGPU_ERR_INVALID, "params is null");
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (prm->max_iterations < 0) return fail(IKGPU_ERR_INVALID, "max_iterations must be >= 0");
+    if (int rc = check_have_params(prm)) return rc;
+    if (int rc = check_problem(p)) return rc;
+    if (int rc = check_max_iterations(prm->max_iterations)) return rc;
     const int levels = p->gen.generic.nlevels;
     if (levels > IKGPU_MAX_PIK_LEVELS)
         return fail(IKGPU_ERR_UNSUPPORTED, "the problem has " + std::to_string(levels) + " priority levels, ik::pik on the device takes at most " +
@@ -211,14 +315,31 @@ int check_pik_params(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
     return IKGPU_OK;
 }
 
+// The model and task arrays a problem is analysed from (ikgpu_problem_create_constrained, _plan_constrained, _precompile).
+int check_problem_inputs(const ikgpu_model *h, const ikgpu_task *tasks, const ikgpu_task *constraints, int32_t nconstraints) {
+    if (!h || !tasks || (nconstraints > 0 && !constraints)) return null_argument();
+    return refuse_if(nconstraints < 0, "negative constraint count");
+}
+
+void copy_name(const std::string &name, char *out, size_t cap) {
+    if (!out || !cap) return;
+    std::strncpy(out, name.c_str(), cap - 1);
+    out[cap - 1] = '\0';
+}
+
+// IKGPU_PIK_KERNEL=generic keeps every ik::pik call on the PIK kernel's interpreter forms (the parity tests compare the routes);
+// =static also keeps it off the DLS and tree kernels, on the compiled lane program where there is one.
+bool pik_forced(bool or_static) {
+    const char *force = std::getenv("IKGPU_PIK_KERNEL");
+    return force && (std::strcmp(force, "generic") == 0 || (or_static && std::strcmp(force, "static") == 0));
+}
+
 // ik::pik with ONE priority level and no secondary velocity is the DLS iteration: P = I, so the level's step is
 // dq = -damp_pinv(J, lambda) e = -J^T (J J^T + lambda^2 I)^-1 e (reference ik/ik/pik.cpp:5-21,47-61 against ik/ik/dls.cpp:39-53),
 // and the stop test, integration and clamp are the same statements in the same order (pik.cpp:67-77, dls.cpp:61-71).
 // ik::pik does not read the problem's constraints, so a problem that has any stays on the PIK kernel.
-// IKGPU_PIK_KERNEL=generic keeps every ik::pik call on the PIK kernel (the parity tests compare the two).
 bool pik_is_one_dls_level(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
-    const char *force = std::getenv("IKGPU_PIK_KERNEL");
-    if (force && (std::strcmp(force, "generic") == 0 || std::strcmp(force, "static") == 0)) return false;
+    if (pik_forced(/*or_static=*/true)) return false;
     return p->gen.generic.nlevels == 1 && !prm->da && prm->lambda[0] > 0.0 && p->host.constraints.empty();
 }
 
@@ -227,22 +348,26 @@ bool pik_is_one_dls_level(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
 // the tree kernel's arrow solve with damping lambda[0], level 1 a rank-one correction on the chain's joints (device/tree_solver.hpp
 // PikRow).  No secondary velocity, lambda > 0 on both levels.
 bool pik_is_two_levels_on_the_tree(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
-    const char *force = std::getenv("IKGPU_PIK_KERNEL");   // generic: the interpreter forms; static: the compiled lane program where there is one
-    if (force && (std::strcmp(force, "generic") == 0 || std::strcmp(force, "static") == 0)) return false;
+    if (pik_forced(/*or_static=*/true)) return false;
     return p->gen.generic.nlevels == 2 && prm->num_levels == 2 && !prm->da && prm->lambda[0] > 0.0 && prm->lambda[1] > 0.0 &&
            p->host.constraints.empty() && ikgpu::tree_takes_two_level_pik(p->host);
+}
+
+// Whether the call has a secondary step at all: a null or all-zero da takes the program without one.
+bool pik_has_da(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
+    bool has_da = false;
+    if (prm->da)
+        for (int k = 0; k < p->gen.nv; ++k) has_da = has_da || prm->da[k] != 0.0;
+    return has_da;
 }
 
 // ik::pik on its compiled lane program: every level's lambda > 0 (the program factors Jbar Jbar^T + lambda^2 I), the program exists
 // (compiled here on first use).  IKGPU_PIK_KERNEL=generic / IKGPU_PIK_STATIC=0 keep the interpreter forms.
 bool pik_runs_static(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
-    const char *force = std::getenv("IKGPU_PIK_KERNEL");
-    if (force && std::strcmp(force, "generic") == 0) return false;
+    if (pik_forced(/*or_static=*/false)) return false;
     for (int l = 0; l < prm->num_levels; ++l)
         if (!(prm->lambda[l] > 0.0)) return false;
-    bool has_da = false;
-    if (prm->da)
-        for (int k = 0; k < p->gen.nv; ++k) has_da = has_da || prm->da[k] != 0.0;
+    const bool has_da = pik_has_da(p, prm);
     const int v = has_da ? 1 : 0;
     if (!ikgpu::rtc_pik_static_available(p->gen, has_da, /*compile=*/false, nullptr)) return false;
     std::call_once(p->pik_static_once[v], [&] {
@@ -251,169 +376,181 @@ bool pik_runs_static(const ikgpu_problem *p, const ikgpu_pik_params *prm) {
     return p->pik_static[v];
 }
 
-// Host-pointer form of a batched solve: copy in, run `launch` on device buffers, synchronise, copy out.
+// Level 0 of an ik::pik call as the parameters of the DLS iteration it is (the derived-visitor members stay off).
+ikgpu_dls_params pik_level0_as_dls(const ikgpu_pik_params *prm) {
+    ikgpu_dls_params d{};
+    d.max_iterations = prm->max_iterations; d.damping = prm->lambda[0]; d.step_length = prm->step_length; d.stop_sq_tol = prm->stop_sq_tol;
+    return d;
+}
+
+constexpr int kNotStaged = -1;   // (no return code: solve_staged left the call to the pipelined path)
+
+// Host-pointer form of a batched solve, small batches: copy in, run `launch` on device buffers, copy out -- or kNotStaged when the
+// batch is too large for the staging area, another thread holds it, or it could not be grown.
+template <class Launch>
+int solve_staged(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets, double *q_out, uint8_t *success, int32_t *iters,
+                 int layout, bool pose7, Launch &launch) {
+    const size_t nb_q = sizeof(double) * p->host.nq * B, nb_t = sizeof(double) * 12 * p->host.ntasks * B;
+    const size_t nb_t7 = pose7 ? sizeof(double) * 7 * p->host.ntasks * B : 0;
+    // Small batches -- the reference's own call pattern is ONE problem per call, 50 times a second (ik_ros/src/cassie.cpp:112)
+    // -- go through a staging area the problem keeps: one pinned host buffer and one device buffer laid out
+    // [q0 | targets | q_out | iters | success], so a call is two copies and a launch instead of five allocations, five
+    // copies, a device synchronise and five frees.  A second thread calling on the same problem meanwhile takes the pipelined path.
+    const size_t off_t = nb_q, off_q = off_t + nb_t, off_i = off_q + nb_q, off_s = off_i + sizeof(int32_t) * B;
+    const size_t off_7 = (off_s + B + 7) / 8 * 8;                  // (pose7 targets land behind everything else)
+    const size_t total = off_7 + nb_t7;
+    if (total > kStageLimit) return kNotStaged;
+    std::unique_lock<std::mutex> lock(p->stage.mu, std::try_to_lock);
+    if (!lock.owns_lock()) return kNotStaged;
+    Staging &st = p->stage;
+    if (st.cap < total) {
+        st.release();
+        const size_t cap = std::max<size_t>(total, 4096);
+        if (hipMalloc(&st.dev, cap) == hipSuccess && hipHostMalloc(&st.host, cap, hipHostMallocDefault) == hipSuccess) st.cap = cap;
+    }
+    if (st.cap < total) return kNotStaged;
+    char *h = static_cast<char *>(st.host), *d = static_cast<char *>(st.dev);
+    std::memcpy(h, q0, nb_q);
+    hipError_t e = hipSuccess;
+    if (pose7) {
+        std::memcpy(h + off_7, targets, nb_t7);
+        e = hipMemcpy(d, h, nb_q, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + off_7, h + off_7, nb_t7, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = ikgpu::launch_targets_from_pose7(B, p->host.ntasks, reinterpret_cast<const double *>(d + off_7),
+                                                                  reinterpret_cast<double *>(d + off_t), layout, nullptr);
+    } else {
+        std::memcpy(h + off_t, targets, nb_t);
+        e = hipMemcpy(d, h, off_q, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) return hip_fail(e, "host-pointer solve (staged copy in)");
+    const int rc = launch(B, reinterpret_cast<double *>(d), reinterpret_cast<double *>(d + off_t), reinterpret_cast<double *>(d + off_q),
+                          reinterpret_cast<uint8_t *>(d + off_s), reinterpret_cast<int32_t *>(d + off_i), nullptr);
+    if (rc != IKGPU_OK) return rc;
+    e = hipMemcpy(h + off_q, d + off_q, total - off_q, hipMemcpyDeviceToHost);   // waits for the launch on the null stream
+    if (e != hipSuccess) return hip_fail(e, "host-pointer solve (staged copy out)");
+    std::memcpy(q_out, h + off_q, nb_q);
+    if (iters) std::memcpy(iters, h + off_i, sizeof(int32_t) * B);
+    if (success) std::memcpy(success, h + off_s, B);
+    return static_cast<int>(IKGPU_OK);
+}
+
+// ... and every other batch: the pipelined path.  Chunk k lives compactly on the device ([rows][b_k], component-major, or [b_k][rows]);
+// for the component-major layout one 2-D copy per array gathers / scatters the chunk's columns of the caller's [rows][B] arrays.
+// Pinned caller buffers make every copy asynchronous; pageable ones still work (the runtime stages them).
+template <class Launch>
+int solve_pipelined(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets, double *q_out, uint8_t *success, int32_t *iters,
+                    int layout, bool pose7, Launch &launch) {
+    static HostTrace trace;
+    const double t_enter = trace.on ? HostTrace::now() : 0.0;
+    std::lock_guard<std::mutex> plock(p->pipe.mu);
+    const double t_locked = trace.on ? HostTrace::now() : 0.0;
+    HostPipe &pp = p->pipe;
+    // Chunks that fill the device: one problem per lane means a launch lasts as long as ONE wave whatever its size, and kernels of
+    // different streams were measured NOT to overlap here (B = 65536 in 8 chunks on 8 streams: 0.93 ms; 2 chunks: 0.55 ms; 1 chunk,
+    // i.e. no overlap at all: 0.61 ms; tools/host_entry_timing.py) -- so two halves up to 131072 problems, 65536 per chunk above
+    // (B = 262144: 1.49 ms against 2.21 unpipelined).
+    int64_t chunk = B <= 131072 ? ((B + 1) / 2 + 63) / 64 * 64 : 65536;
+    if (const char *env = std::getenv("IKGPU_HOST_CHUNK")) { const long c = std::strtol(env, nullptr, 10); if (c >= 64) chunk = c; }
+    const int64_t nchunks = (B + chunk - 1) / chunk;
+    const size_t nq = static_cast<size_t>(p->host.nq), nt = static_cast<size_t>(12 * p->host.ntasks);
+    const size_t nt7 = pose7 ? static_cast<size_t>(7 * p->host.ntasks) : 0;
+    const size_t per_problem = 8 * nq + 8 * nt + 8 * nq + 4 + 1 + 8 * nt7;
+    const size_t need = per_problem * static_cast<size_t>(B) + 64 * static_cast<size_t>(nchunks) * 6;   // (every array 64-byte aligned)
+    hipError_t e = hipSuccess;
+    auto step = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (!pp.in) {
+        step(hipStreamCreateWithFlags(&pp.in, hipStreamNonBlocking));
+        step(hipStreamCreateWithFlags(&pp.out, hipStreamNonBlocking));
+        for (hipStream_t &r : pp.run) step(hipStreamCreateWithFlags(&r, hipStreamNonBlocking));
+    }
+    if (e == hipSuccess && pp.cap < need) {
+        if (pp.dev) { (void)hipFree(pp.dev); pp.dev = nullptr; pp.cap = 0; }   // (every call leaves its streams idle)
+        step(hipMalloc(&pp.dev, need));
+        if (e == hipSuccess) pp.cap = need;
+    }
+    while (e == hipSuccess && static_cast<int64_t>(pp.ev_in.size()) < nchunks) {
+        hipEvent_t a = nullptr, b = nullptr;
+        step(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+        step(hipEventCreateWithFlags(&b, hipEventDisableTiming));
+        if (e == hipSuccess) { pp.ev_in.push_back(a); pp.ev_run.push_back(b); }
+    }
+    if (e != hipSuccess) return hip_fail(e, "host-pointer solve (pipeline set-up)");
+    char *cur = static_cast<char *>(pp.dev);
+    auto take = [&](size_t bytes) { char *r = cur; cur += (bytes + 63) / 64 * 64; return r; };
+    const bool soa = layout == IKGPU_SOA;
+    // rows x [b0, b0 + bk) of a host array with B columns  <->  a compact rows x bk device array (SoA), or bk x rows contiguous (AoS)
+    auto copy = [&](void *dev, const void *host_c, void *host, size_t rows, size_t elem, int64_t b0, int64_t bk, bool to_device, hipStream_t st) {
+        if (soa && rows > 1) {
+            const size_t w = static_cast<size_t>(bk) * elem, hp = static_cast<size_t>(B) * elem;
+            return to_device ? hipMemcpy2DAsync(dev, w, static_cast<const char *>(host_c) + static_cast<size_t>(b0) * elem, hp, w, rows, hipMemcpyHostToDevice, st)
+                             : hipMemcpy2DAsync(static_cast<char *>(host) + static_cast<size_t>(b0) * elem, hp, dev, w, w, rows, hipMemcpyDeviceToHost, st);
+        }
+        const size_t off = static_cast<size_t>(b0) * rows * elem, bytes = static_cast<size_t>(bk) * rows * elem;
+        return to_device ? hipMemcpyAsync(dev, static_cast<const char *>(host_c) + off, bytes, hipMemcpyHostToDevice, st)
+                         : hipMemcpyAsync(static_cast<char *>(host) + off, dev, bytes, hipMemcpyDeviceToHost, st);
+    };
+    int rc = IKGPU_OK;
+    const double t_setup = trace.on ? HostTrace::now() : 0.0;
+    for (int64_t k = 0; k < nchunks && rc == IKGPU_OK && e == hipSuccess; ++k) {
+        const int64_t b0 = k * chunk, bk = std::min<int64_t>(chunk, B - b0);
+        double *d_q0 = reinterpret_cast<double *>(take(8 * nq * bk)), *d_t = reinterpret_cast<double *>(take(8 * nt * bk));
+        double *d_q = reinterpret_cast<double *>(take(8 * nq * bk));
+        int32_t *d_i = reinterpret_cast<int32_t *>(take(4 * bk));
+        uint8_t *d_s = reinterpret_cast<uint8_t *>(take(bk));
+        double *d_t7 = pose7 ? reinterpret_cast<double *>(take(8 * nt7 * bk)) : nullptr;
+        step(copy(d_q0, q0, nullptr, nq, 8, b0, bk, true, pp.in));
+        if (pose7) step(copy(d_t7, targets, nullptr, nt7, 8, b0, bk, true, pp.in));
+        else step(copy(d_t, targets, nullptr, nt, 8, b0, bk, true, pp.in));
+        step(hipEventRecord(pp.ev_in[k], pp.in));
+        const hipStream_t run = pp.run[k % HostPipe::kRunStreams];
+        step(hipStreamWaitEvent(run, pp.ev_in[k], 0));
+        if (pose7) step(ikgpu::launch_targets_from_pose7(bk, p->host.ntasks, d_t7, d_t, layout, run));
+        if (e != hipSuccess) break;
+        rc = launch(bk, d_q0, d_t, d_q, d_s, d_i, run);
+        if (rc != IKGPU_OK) break;
+        step(hipEventRecord(pp.ev_run[k], run));
+        step(hipStreamWaitEvent(pp.out, pp.ev_run[k], 0));
+        step(copy(d_q, nullptr, q_out, nq, 8, b0, bk, false, pp.out));
+        if (iters) step(copy(d_i, nullptr, iters, 1, 4, b0, bk, false, pp.out));
+        if (success) step(copy(d_s, nullptr, success, 1, 1, b0, bk, false, pp.out));
+    }
+    // The arena is reused by the next call: everything in flight has to land first.  When every chunk was enqueued, the copy-out
+    // stream is the LAST link of every chain (in -> run[k] -> out, by events), so one wait on it covers all three; after a failure
+    // half way through every stream that was touched is waited for.  (Round 3 waited for all ten streams, used or not.)
+    const double t_enqueued = trace.on ? HostTrace::now() : 0.0;
+    hipError_t w = hipSuccess;
+    if (rc != IKGPU_OK || e != hipSuccess) {
+        w = hipStreamSynchronize(pp.in);
+        for (int64_t k = 0; k < std::min<int64_t>(nchunks, HostPipe::kRunStreams); ++k) { const hipError_t x = hipStreamSynchronize(pp.run[k]); if (w == hipSuccess) w = x; }
+    }
+    { const hipError_t x = hipStreamSynchronize(pp.out); if (w == hipSuccess) w = x; }
+    if (trace.on) {
+        const double t_done = HostTrace::now();
+        std::fprintf(trace.f, "B %lld chunks %lld total_ms %.4f lock %.4f setup %.4f enqueue %.4f wait %.4f\n", static_cast<long long>(B),
+                     static_cast<long long>(nchunks), t_done - t_enter, t_locked - t_enter, t_setup - t_locked, t_enqueued - t_setup, t_done - t_enqueued);
+        std::fflush(trace.f);
+    }
+    if (rc != IKGPU_OK) return rc;
+    step(w);
+    if (e != hipSuccess) return hip_fail(e, "host-pointer solve (pipeline)");
+    return static_cast<int>(IKGPU_OK);
+}
+
+// Host-pointer form of a batched solve, on the problem's device: the staging area when it takes the batch, else the pipeline.
 template <class Launch>
 int host_solve(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets, double *q_out, uint8_t *success,
                int32_t *iters, int layout_in, Launch &&launch) {
     const bool pose7 = (layout_in & IKGPU_TARGETS_POSE7) != 0;   // targets arrive as 7 doubles per task and are expanded on the device
     const int layout = layout_in & ~IKGPU_TARGETS_POSE7;
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const size_t nb_q = sizeof(double) * p->host.nq * B, nb_t = sizeof(double) * 12 * p->host.ntasks * B;
-        const size_t nb_t7 = pose7 ? sizeof(double) * 7 * p->host.ntasks * B : 0;
-        // Small batches -- the reference's own call pattern is ONE problem per call, 50 times a second (ik_ros/src/cassie.cpp:112)
-        // -- go through a staging area the problem keeps: one pinned host buffer and one device buffer laid out
-        // [q0 | targets | q_out | iters | success], so a call is two copies and a launch instead of five allocations, five
-        // copies, a device synchronise and five frees.  A second thread calling on the same problem meanwhile takes the path below.
-        const size_t off_t = nb_q, off_q = off_t + nb_t, off_i = off_q + nb_q, off_s = off_i + sizeof(int32_t) * B;
-        const size_t off_7 = (off_s + B + 7) / 8 * 8;                  // (pose7 targets land behind everything else)
-        const size_t total = off_7 + nb_t7;
-        if (total <= kStageLimit) {
-            std::unique_lock<std::mutex> lock(p->stage.mu, std::try_to_lock);
-            if (lock.owns_lock()) {
-                Staging &st = p->stage;
-                if (st.cap < total) {
-                    if (st.dev) (void)hipFree(st.dev);
-                    if (st.host) (void)hipHostFree(st.host);
-                    st.dev = st.host = nullptr;
-                    st.cap = 0;
-                    const size_t cap = std::max<size_t>(total, 4096);
-                    if (hipMalloc(&st.dev, cap) == hipSuccess && hipHostMalloc(&st.host, cap, hipHostMallocDefault) == hipSuccess) st.cap = cap;
-                }
-                if (st.cap >= total) {
-                    char *h = static_cast<char *>(st.host), *d = static_cast<char *>(st.dev);
-                    std::memcpy(h, q0, nb_q);
-                    hipError_t e = hipSuccess;
-                    if (pose7) {
-                        std::memcpy(h + off_7, targets, nb_t7);
-                        e = hipMemcpy(d, h, nb_q, hipMemcpyHostToDevice);
-                        if (e == hipSuccess) e = hipMemcpy(d + off_7, h + off_7, nb_t7, hipMemcpyHostToDevice);
-                        if (e == hipSuccess) e = ikgpu::launch_targets_from_pose7(B, p->host.ntasks, reinterpret_cast<const double *>(d + off_7),
-                                                                                  reinterpret_cast<double *>(d + off_t), layout, nullptr);
-                    } else {
-                        std::memcpy(h + off_t, targets, nb_t);
-                        e = hipMemcpy(d, h, off_q, hipMemcpyHostToDevice);
-                    }
-                    if (e != hipSuccess) return hip_fail(e, "host-pointer solve (staged copy in)");
-                    const int rc = launch(B, reinterpret_cast<double *>(d), reinterpret_cast<double *>(d + off_t), reinterpret_cast<double *>(d + off_q),
-                                          reinterpret_cast<uint8_t *>(d + off_s), reinterpret_cast<int32_t *>(d + off_i), nullptr);
-                    if (rc != IKGPU_OK) return rc;
-                    e = hipMemcpy(h + off_q, d + off_q, total - off_q, hipMemcpyDeviceToHost);   // waits for the launch on the null stream
-                    if (e != hipSuccess) return hip_fail(e, "host-pointer solve (staged copy out)");
-                    std::memcpy(q_out, h + off_q, nb_q);
-                    if (iters) std::memcpy(iters, h + off_i, sizeof(int32_t) * B);
-                    if (success) std::memcpy(success, h + off_s, B);
-                    return static_cast<int>(IKGPU_OK);
-                }
-            }
-        }
-        // The pipelined path.  Chunk k lives compactly on the device ([rows][b_k], component-major, or [b_k][rows]); for the
-        // component-major layout one 2-D copy per array gathers / scatters the chunk's columns of the caller's [rows][B] arrays.
-        // Pinned caller buffers make every copy asynchronous; pageable ones still work (the runtime stages them).
-        static HostTrace trace;
-        const double t_enter = trace.on ? HostTrace::now() : 0.0;
-        std::lock_guard<std::mutex> plock(p->pipe.mu);
-        const double t_locked = trace.on ? HostTrace::now() : 0.0;
-        HostPipe &pp = p->pipe;
-        // Chunks that fill the device: one problem per lane means a launch lasts as long as ONE wave whatever its size, and kernels of
-        // different streams were measured NOT to overlap here (B = 65536 in 8 chunks on 8 streams: 0.93 ms; 2 chunks: 0.55 ms; 1 chunk,
-        // i.e. no overlap at all: 0.61 ms; tools/host_entry_timing.py) -- so two halves up to 131072 problems, 65536 per chunk above
-        // (B = 262144: 1.49 ms against 2.21 unpipelined).
-        int64_t chunk = B <= 131072 ? ((B + 1) / 2 + 63) / 64 * 64 : 65536;
-        if (const char *env = std::getenv("IKGPU_HOST_CHUNK")) { const long c = std::strtol(env, nullptr, 10); if (c >= 64) chunk = c; }
-        const int64_t nchunks = (B + chunk - 1) / chunk;
-        const size_t nq = static_cast<size_t>(p->host.nq), nt = static_cast<size_t>(12 * p->host.ntasks);
-        const size_t nt7 = pose7 ? static_cast<size_t>(7 * p->host.ntasks) : 0;
-        const size_t per_problem = 8 * nq + 8 * nt + 8 * nq + 4 + 1 + 8 * nt7;
-        const size_t need = per_problem * static_cast<size_t>(B) + 64 * static_cast<size_t>(nchunks) * 6;   // (every array 64-byte aligned)
-        hipError_t e = hipSuccess;
-        auto step = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-        if (!pp.in) {
-            step(hipStreamCreateWithFlags(&pp.in, hipStreamNonBlocking));
-            step(hipStreamCreateWithFlags(&pp.out, hipStreamNonBlocking));
-            for (hipStream_t &r : pp.run) step(hipStreamCreateWithFlags(&r, hipStreamNonBlocking));
-        }
-        if (e == hipSuccess && pp.cap < need) {
-            if (pp.dev) { (void)hipFree(pp.dev); pp.dev = nullptr; pp.cap = 0; }   // (every call leaves its streams idle)
-            step(hipMalloc(&pp.dev, need));
-            if (e == hipSuccess) pp.cap = need;
-        }
-        while (e == hipSuccess && static_cast<int64_t>(pp.ev_in.size()) < nchunks) {
-            hipEvent_t a = nullptr, b = nullptr;
-            step(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-            step(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-            if (e == hipSuccess) { pp.ev_in.push_back(a); pp.ev_run.push_back(b); }
-        }
-        if (e != hipSuccess) return hip_fail(e, "host-pointer solve (pipeline set-up)");
-        char *cur = static_cast<char *>(pp.dev);
-        auto take = [&](size_t bytes) { char *r = cur; cur += (bytes + 63) / 64 * 64; return r; };
-        const bool soa = layout == IKGPU_SOA;
-        // rows x [b0, b0 + bk) of a host array with B columns  <->  a compact rows x bk device array (SoA), or bk x rows contiguous (AoS)
-        auto copy = [&](void *dev, const void *host_c, void *host, size_t rows, size_t elem, int64_t b0, int64_t bk, bool to_device, hipStream_t st) {
-            if (soa && rows > 1) {
-                const size_t w = static_cast<size_t>(bk) * elem, hp = static_cast<size_t>(B) * elem;
-                return to_device ? hipMemcpy2DAsync(dev, w, static_cast<const char *>(host_c) + static_cast<size_t>(b0) * elem, hp, w, rows, hipMemcpyHostToDevice, st)
-                                 : hipMemcpy2DAsync(static_cast<char *>(host) + static_cast<size_t>(b0) * elem, hp, dev, w, w, rows, hipMemcpyDeviceToHost, st);
-            }
-            const size_t off = static_cast<size_t>(b0) * rows * elem, bytes = static_cast<size_t>(bk) * rows * elem;
-            return to_device ? hipMemcpyAsync(dev, static_cast<const char *>(host_c) + off, bytes, hipMemcpyHostToDevice, st)
-                             : hipMemcpyAsync(static_cast<char *>(host) + off, dev, bytes, hipMemcpyDeviceToHost, st);
-        };
-        int rc = IKGPU_OK;
-        const double t_setup = trace.on ? HostTrace::now() : 0.0;
-        for (int64_t k = 0; k < nchunks && rc == IKGPU_OK && e == hipSuccess; ++k) {
-            const int64_t b0 = k * chunk, bk = std::min<int64_t>(chunk, B - b0);
-            double *d_q0 = reinterpret_cast<double *>(take(8 * nq * bk)), *d_t = reinterpret_cast<double *>(take(8 * nt * bk));
-            double *d_q = reinterpret_cast<double *>(take(8 * nq * bk));
-            int32_t *d_i = reinterpret_cast<int32_t *>(take(4 * bk));
-            uint8_t *d_s = reinterpret_cast<uint8_t *>(take(bk));
-            double *d_t7 = pose7 ? reinterpret_cast<double *>(take(8 * nt7 * bk)) : nullptr;
-            step(copy(d_q0, q0, nullptr, nq, 8, b0, bk, true, pp.in));
-            if (pose7) step(copy(d_t7, targets, nullptr, nt7, 8, b0, bk, true, pp.in));
-            else step(copy(d_t, targets, nullptr, nt, 8, b0, bk, true, pp.in));
-            step(hipEventRecord(pp.ev_in[k], pp.in));
-            const hipStream_t run = pp.run[k % HostPipe::kRunStreams];
-            step(hipStreamWaitEvent(run, pp.ev_in[k], 0));
-            if (pose7) step(ikgpu::launch_targets_from_pose7(bk, p->host.ntasks, d_t7, d_t, layout, run));
-            if (e != hipSuccess) break;
-            rc = launch(bk, d_q0, d_t, d_q, d_s, d_i, run);
-            if (rc != IKGPU_OK) break;
-            step(hipEventRecord(pp.ev_run[k], run));
-            step(hipStreamWaitEvent(pp.out, pp.ev_run[k], 0));
-            step(copy(d_q, nullptr, q_out, nq, 8, b0, bk, false, pp.out));
-            if (iters) step(copy(d_i, nullptr, iters, 1, 4, b0, bk, false, pp.out));
-            if (success) step(copy(d_s, nullptr, success, 1, 1, b0, bk, false, pp.out));
-        }
-        // The arena is reused by the next call: everything in flight has to land first.  When every chunk was enqueued, the copy-out
-        // stream is the LAST link of every chain (in -> run[k] -> out, by events), so one wait on it covers all three; after a failure
-        // half way through every stream that was touched is waited for.  (Round 3 waited for all ten streams, used or not.)
-        const double t_enqueued = trace.on ? HostTrace::now() : 0.0;
-        hipError_t w = hipSuccess;
-        if (rc != IKGPU_OK || e != hipSuccess) {
-            w = hipStreamSynchronize(pp.in);
-            for (int64_t k = 0; k < std::min<int64_t>(nchunks, HostPipe::kRunStreams); ++k) { const hipError_t x = hipStreamSynchronize(pp.run[k]); if (w == hipSuccess) w = x; }
-        }
-        { const hipError_t x = hipStreamSynchronize(pp.out); if (w == hipSuccess) w = x; }
-        if (trace.on) {
-            const double t_done = HostTrace::now();
-            std::fprintf(trace.f, "B %lld chunks %lld total_ms %.4f lock %.4f setup %.4f enqueue %.4f wait %.4f\n", static_cast<long long>(B),
-                         static_cast<long long>(nchunks), t_done - t_enter, t_locked - t_enter, t_setup - t_locked, t_enqueued - t_setup, t_done - t_enqueued);
-            std::fflush(trace.f);
-        }
-        if (rc != IKGPU_OK) return rc;
-        step(w);
-        if (e != hipSuccess) return hip_fail(e, "host-pointer solve (pipeline)");
-        return static_cast<int>(IKGPU_OK);
+    return on_device(p->device, nullptr, [&](hipStream_t) {
+        const int rc = solve_staged(p, B, q0, targets, q_out, success, iters, layout, pose7, launch);
+        return rc != kNotStaged ? rc : solve_pipelined(p, B, q0, targets, q_out, success, iters, layout, pose7, launch);
     });
 }
 
-}  // namespace
-
-namespace {
 int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_dls_params *params, hipStream_t st);
-int dispatch_eval(const ikgpu_problem *p, int64_t B, const double *q, const double *targets, double *e_out, double *J_out, int layout, hipStream_t st);
-}
+
+}  // namespace
 
 extern "C" {
 
@@ -433,7 +570,7 @@ void ikgpu_dls_params_default(ikgpu_dls_params *p) {
 }
 
 int ikgpu_model_from_urdf(const char *xml, size_t len, int root_joint, ikgpu_model **out) {
-    if (!xml || !out) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (!xml || !out) return null_argument();
     if (root_joint != IKGPU_ROOT_FIXED && root_joint != IKGPU_ROOT_FREEFLYER)
         return fail(IKGPU_ERR_INVALID, "root_joint must be IKGPU_ROOT_FIXED or IKGPU_ROOT_FREEFLYER");
     *out = nullptr;
@@ -450,7 +587,7 @@ int ikgpu_model_from_urdf(const char *xml, size_t len, int root_joint, ikgpu_mod
 }
 
 int ikgpu_model_create(const ikgpu_flat_model *flat, ikgpu_model **out) {
-    if (!flat || !out) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (!flat || !out) return null_argument();
     *out = nullptr;
     return guarded([&] {
         auto *h = new ikgpu_model{ikgpu::Model::from_flat(*flat)};
@@ -463,7 +600,7 @@ int ikgpu_model_create(const ikgpu_flat_model *flat, ikgpu_model **out) {
 void ikgpu_model_destroy(ikgpu_model *m) { delete m; }
 
 int ikgpu_model_get_flat(const ikgpu_model *h, ikgpu_flat_model *out) {
-    if (!h || !out) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (!h || !out) return null_argument();
     const ikgpu::Model &m = h->m;
     out->njoints = m.njoints();
     out->nq = m.nq;
@@ -503,79 +640,60 @@ int ikgpu_problem_create(const ikgpu_model *h, const ikgpu_task *tasks, int32_t 
 
 int ikgpu_problem_create_constrained(const ikgpu_model *h, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
                                      int32_t nconstraints, int32_t device, ikgpu_problem **out) {
-    if (!h || !tasks || !out || (nconstraints > 0 && !constraints)) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (nconstraints < 0) return fail(IKGPU_ERR_INVALID, "negative constraint count");
+    if (!out) return null_argument();
+    if (int rc = check_problem_inputs(h, tasks, constraints, nconstraints)) return rc;
     *out = nullptr;
-    ikgpu::ProblemHost ph, gen;
-    try {
-        ph = analyse(h->m, tasks, ntasks, constraints, nconstraints, /*compile_rtc=*/true);
-        gen = ph.kind == ikgpu::KernelKind::Generic
-                  ? ph
-                  : ikgpu::analyse_problem(h->m, tasks, ntasks, /*force_generic=*/true, constraints, nconstraints);
-    } catch (const std::exception &e) {
-        return fail(IKGPU_ERR_INVALID, e.what());
-    }
-
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0) return fail(IKGPU_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(IKGPU_ERR_INVALID, "device ordinal out of range");
-    hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(IKGPU_ERR_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-
     return guarded([&] {
-        DeviceGuard g(device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        auto *p = new ikgpu_problem;
-        p->host = std::move(ph);
-        p->gen = std::move(gen);
-        p->dls_name = p->host.kernel_name;
-        if (tree_prefers_static(p->host) && ikgpu::rtc_generic_static_available(p->gen, /*compile=*/true, &p->gen.generic_key)) {
-            p->gen.generic_build = 2;
-            p->dls_on_static_gen = true;
-            p->dls_name = static_name(p->gen);
-        }
-        if (p->host.kind == ikgpu::KernelKind::Generic) {   // (analyse() compiled it: gen is a copy of host)
-            p->gen.generic_build = p->host.generic_build;
-            p->gen.generic_key = p->host.generic_key;
-        }
-        {
-            std::string gname = p->gen.kernel_name;   // ("...,static>": the DLS program's build, not ik::pik's)
-            const size_t st = gname.find(",static>");
-            if (st != std::string::npos) gname = gname.substr(0, st) + ">";
-            p->pik_name = "pik_generic" + gname.substr(std::min(gname.find('<'), gname.size()));
-        }
-        p->pik_tree_name = p->host.kernel_name.substr(0, p->host.kernel_name.size() - (p->host.kernel_name.empty() ? 0 : 1)) + ",pik_levels=2>";
-        p->device = device;
-        p->nframes = h->m.nframes();
-        const size_t nq = static_cast<size_t>(p->host.nq);
-        hipError_t err = hipSuccess;
-        auto up = [&](auto **dst, const void *src, size_t bytes) {
-            if (err != hipSuccess) return;
-            err = hipMalloc(reinterpret_cast<void **>(dst), bytes ? bytes : 8);
-            if (err == hipSuccess && bytes) err = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        };
-        up(&p->dev.lower, p->host.lower.data(), nq * sizeof(double));
-        up(&p->dev.upper, p->host.upper.data(), nq * sizeof(double));
-        up(&p->dev.q_in_chain, p->host.q_in_chain.data(), nq);
-        p->draw = ikgpu::multistart_draw_mask(h->m, p->host);
-        up(&p->dev.draw, p->draw.data(), nq);
-        up(&p->dev.g_ints, p->gen.generic.ints.data(), p->gen.generic.ints.size() * sizeof(int32_t));
-        up(&p->dev.g_dbls, p->gen.generic.dbls.data(), p->gen.generic.dbls.size() * sizeof(double));
-        if (err == hipSuccess) err = p->dev.queues.grow();
-        if (p->host.kind != ikgpu::KernelKind::Generic) {
-            const std::vector<double> desc = p->host.kind == ikgpu::KernelKind::Chain ? ikgpu::chain_desc_table(p->host)
-                                                                                     : ikgpu::tree_desc_table(p->host);
-            up(&p->dev.chain_desc, desc.data(), desc.size() * sizeof(double));
-        }
-        if (err != hipSuccess) {
-            ikgpu_problem_destroy(p);
-            return hip_fail(err, "uploading problem tables");
-        }
-        *out = p;
-        return static_cast<int>(IKGPU_OK);
+        KernelPlan plan = plan_kernels(h->m, tasks, ntasks, constraints, nconstraints, /*compile=*/true);
+
+        int ndev = 0;
+        hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess || ndev == 0) return fail(IKGPU_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
+        if (device < 0 || device >= ndev) return fail(IKGPU_ERR_INVALID, "device ordinal out of range");
+        hipDeviceProp_t prop;
+        if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return fail(IKGPU_ERR_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+
+        return on_device(device, nullptr, [&](hipStream_t) {
+            std::unique_ptr<ikgpu_problem> p(new ikgpu_problem(device));   // (a failure below deletes it, and with it what was uploaded)
+            p->host = std::move(plan.host);
+            p->gen = std::move(plan.gen);
+            p->dls_on_static_gen = plan.dls_on_static_gen;
+            p->dls_name = plan.name;
+            {
+                std::string gname = p->gen.kernel_name;   // ("...,static>": the DLS program's build, not ik::pik's)
+                const size_t st = gname.find(",static>");
+                if (st != std::string::npos) gname = gname.substr(0, st) + ">";
+                p->pik_name = "pik_generic" + gname.substr(std::min(gname.find('<'), gname.size()));
+            }
+            p->pik_static_name = p->pik_name.substr(0, p->pik_name.size() - 1) + ",static>";
+            p->pik_tree_name = p->host.kernel_name.substr(0, p->host.kernel_name.size() - (p->host.kernel_name.empty() ? 0 : 1)) + ",pik_levels=2>";
+            p->nframes = h->m.nframes();
+            const size_t nq = static_cast<size_t>(p->host.nq);
+            hipError_t err = hipSuccess;
+            auto up = [&](auto **dst, const void *src, size_t bytes) {
+                if (err != hipSuccess) return;
+                err = hipMalloc(reinterpret_cast<void **>(dst), bytes ? bytes : 8);
+                if (err == hipSuccess && bytes) err = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+            };
+            up(&p->dev.lower, p->host.lower.data(), nq * sizeof(double));
+            up(&p->dev.upper, p->host.upper.data(), nq * sizeof(double));
+            up(&p->dev.q_in_chain, p->host.q_in_chain.data(), nq);
+            p->draw = ikgpu::multistart_draw_mask(h->m, p->host);
+            up(&p->dev.draw, p->draw.data(), nq);
+            up(&p->dev.g_ints, p->gen.generic.ints.data(), p->gen.generic.ints.size() * sizeof(int32_t));
+            up(&p->dev.g_dbls, p->gen.generic.dbls.data(), p->gen.generic.dbls.size() * sizeof(double));
+            if (err == hipSuccess) err = p->dev.queues.grow();
+            if (p->host.kind != ikgpu::KernelKind::Generic) {
+                const std::vector<double> desc = p->host.kind == ikgpu::KernelKind::Chain ? ikgpu::chain_desc_table(p->host)
+                                                                                         : ikgpu::tree_desc_table(p->host);
+                up(&p->dev.chain_desc, desc.data(), desc.size() * sizeof(double));
+            }
+            if (err != hipSuccess) return hip_fail(err, "uploading problem tables");
+            *out = p.release();
+            return static_cast<int>(IKGPU_OK);
+        });
     });
 }
 
@@ -585,84 +703,34 @@ int ikgpu_problem_plan(const ikgpu_model *h, const ikgpu_task *tasks, int32_t nt
 
 int ikgpu_problem_plan_constrained(const ikgpu_model *h, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
                                    int32_t nconstraints, char *out, size_t cap) {
-    if (!h || !tasks || (nconstraints > 0 && !constraints)) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (nconstraints < 0) return fail(IKGPU_ERR_INVALID, "negative constraint count");
-    try {
-        const ikgpu::ProblemHost ph = analyse(h->m, tasks, ntasks, constraints, nconstraints);
-        std::string name = ph.kernel_name;
-        if (tree_prefers_static(ph)) {
-            const ikgpu::ProblemHost gen = ikgpu::analyse_problem(h->m, tasks, ntasks, /*force_generic=*/true, constraints, nconstraints);
-            if (ikgpu::rtc_generic_static_available(gen, /*compile=*/false, nullptr)) name = static_name(gen);
-        }
-        if (out && cap) {
-            std::strncpy(out, name.c_str(), cap - 1);
-            out[cap - 1] = '\0';
-        }
-        return IKGPU_OK;
-    } catch (const std::exception &e) {
-        return fail(IKGPU_ERR_INVALID, e.what());
-    }
+    if (int rc = check_problem_inputs(h, tasks, constraints, nconstraints)) return rc;
+    return guarded([&] {
+        copy_name(plan_kernels(h->m, tasks, ntasks, constraints, nconstraints, /*compile=*/false).name, out, cap);
+        return static_cast<int>(IKGPU_OK);
+    });
 }
 
 int ikgpu_problem_precompile(const ikgpu_model *h, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
                              int32_t nconstraints, char *out, size_t cap) {
-    if (!h || !tasks || (nconstraints > 0 && !constraints)) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (nconstraints < 0) return fail(IKGPU_ERR_INVALID, "negative constraint count");
-    try {
-        const ikgpu::ProblemHost planned = analyse(h->m, tasks, ntasks, constraints, nconstraints, /*compile_rtc=*/false);
-        const ikgpu::ProblemHost ph = analyse(h->m, tasks, ntasks, constraints, nconstraints, /*compile_rtc=*/true);
-        std::string want = planned.kernel_name, got = ph.kernel_name;
-        if (tree_prefers_static(ph)) {
-            ikgpu::ProblemHost gen = ikgpu::analyse_problem(h->m, tasks, ntasks, /*force_generic=*/true, constraints, nconstraints);
-            if (ikgpu::rtc_generic_static_available(gen, /*compile=*/false, nullptr)) {
-                want = static_name(gen);
-                if (ikgpu::rtc_generic_static_available(gen, /*compile=*/true, &gen.generic_key)) {
-                    got = want;
-                    (void)ikgpu::rtc_generic_static_precompile_refill(gen);
-                }
-            }
-        } else if (ph.generic_build == 2) {
-            (void)ikgpu::rtc_generic_static_precompile_refill(ph);
-        }
-        {   // a problem with several priority levels may be handed to ik::pik: its compiled lane program (without the secondary step)
-            const ikgpu::ProblemHost gen = ph.kind == ikgpu::KernelKind::Generic
-                                               ? ph : ikgpu::analyse_problem(h->m, tasks, ntasks, /*force_generic=*/true, constraints, nconstraints);
-            // (one level needs the program only for a secondary step, da != 0: compiled at the first such call)
-            if (gen.generic.nlevels >= 2 && ikgpu::rtc_pik_static_available(gen, false, /*compile=*/false, nullptr))
-                (void)ikgpu::rtc_pik_static_available(gen, false, /*compile=*/true, nullptr);
-        }
-        if (out && cap) {
-            std::strncpy(out, got.c_str(), cap - 1);
-            out[cap - 1] = '\0';
-        }
-        if (want != got)   // planned a run-time compiled build, got the pre-built one
-            return fail(IKGPU_ERR_UNSUPPORTED, "run-time compilation failed, the problem runs on " + got + ": " + ikgpu::rtc_last_log());
-        return IKGPU_OK;
-    } catch (const std::exception &e) {
-        return fail(IKGPU_ERR_INVALID, e.what());
-    }
+    if (int rc = check_problem_inputs(h, tasks, constraints, nconstraints)) return rc;
+    return guarded([&] {
+        const std::string want = plan_kernels(h->m, tasks, ntasks, constraints, nconstraints, /*compile=*/false).name;
+        const KernelPlan got = plan_kernels(h->m, tasks, ntasks, constraints, nconstraints, /*compile=*/true);
+        // the refill twin of the static lane program ik::dls runs on, a Tree problem's or a Generic problem's own
+        if (got.dls_on_static_gen) (void)ikgpu::rtc_generic_static_precompile_refill(got.gen);
+        else if (got.host.generic_build == 2) (void)ikgpu::rtc_generic_static_precompile_refill(got.host);
+        // a problem with several priority levels may be handed to ik::pik: its compiled lane program (without the secondary step)
+        // (one level needs the program only for a secondary step, da != 0: compiled at the first such call)
+        if (got.gen.generic.nlevels >= 2 && ikgpu::rtc_pik_static_available(got.gen, false, /*compile=*/false, nullptr))
+            (void)ikgpu::rtc_pik_static_available(got.gen, false, /*compile=*/true, nullptr);
+        copy_name(got.name, out, cap);
+        if (want != got.name)   // planned a run-time compiled build, got the pre-built one
+            return fail(IKGPU_ERR_UNSUPPORTED, "run-time compilation failed, the problem runs on " + got.name + ": " + ikgpu::rtc_last_log());
+        return static_cast<int>(IKGPU_OK);
+    });
 }
 
-void ikgpu_problem_destroy(ikgpu_problem *p) {
-    if (!p) return;
-    DeviceGuard g(p->device);
-    (void)hipFree(p->dev.lower);
-    (void)hipFree(p->dev.upper);
-    (void)hipFree(p->dev.q_in_chain);
-    (void)hipFree(p->dev.draw);
-    (void)hipFree(p->dev.chain_desc);
-    (void)hipFree(p->dev.g_ints);
-    (void)hipFree(p->dev.g_dbls);
-    p->dev.queues.release();
-    if (p->pipe.dev) (void)hipFree(p->pipe.dev);
-    for (hipEvent_t ev : p->pipe.ev_in) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : p->pipe.ev_run) (void)hipEventDestroy(ev);
-    if (p->pipe.in) { (void)hipStreamDestroy(p->pipe.in); (void)hipStreamDestroy(p->pipe.out); }
-    for (hipStream_t r : p->pipe.run) if (r) (void)hipStreamDestroy(r);
-    if (p->stage.dev) (void)hipFree(p->stage.dev);
-    if (p->stage.host) (void)hipHostFree(p->stage.host);
-    delete p;
-}
+void ikgpu_problem_destroy(ikgpu_problem *p) { delete p; }
 
 int32_t ikgpu_problem_rows(const ikgpu_problem *p) { return p ? p->host.rows : -1; }
 
@@ -677,17 +745,14 @@ int ikgpu_problem_support(const ikgpu_problem *p, uint8_t *support) {
 int ikgpu_dls_solve_batch(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets,
                           const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters, int layout,
                           void *stream) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_layout(layout)) return rc;
     if (int rc = check_params(params)) return rc;
     if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null)
-    if (!q0 || !targets || !q_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B > (int64_t(1) << 31) * 32) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        return dispatch_dls(p, ikgpu::BatchIO{B, q0, targets, q_out, success, iters, layout}, params, static_cast<hipStream_t>(stream));
+    if (!q0 || !targets || !q_out) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        return dispatch_dls(p, ikgpu::BatchIO{B, q0, targets, q_out, success, iters, layout}, params, st);
     });
 }
 
@@ -695,8 +760,8 @@ int ikgpu_dls_solve_batch(const ikgpu_problem *p, int64_t B, const double *q0, c
 
 namespace {
 
-// The kernel dispatch of ikgpu_dls_solve_batch for validated arguments, on the problem's device, inside `guarded` (the launchers
-// throw for a shape without an instantiation).  ikgpu_dls_track_batch loops over it for the problem kinds without a tracking kernel.
+// The kernel dispatch of ikgpu_dls_solve_batch for validated arguments, inside on_device.  ikgpu_dls_track_batch loops over it for
+// the problem kinds without a tracking kernel, run_starts for the multi-start and solution-set definitions.
 int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_dls_params *params, hipStream_t st) {
     if (ikgpu::visitor_extended(*params)) {
         // a derived visitor (step tolerance / per-level tolerances): the generic lane program implements the family -- the one
@@ -709,19 +774,17 @@ int dispatch_dls(const ikgpu_problem *p, const ikgpu::BatchIO &io, const ikgpu_d
         const uint64_t key = p->gen.generic_build == 2 ? p->gen.generic_key : p->visitor_static_key;
         const hipError_t ev = on_static ? ikgpu::rtc_launch_generic_static(p->gen, key, io, *params, st, p->dev.queues)
                                         : ikgpu::launch_dls_generic(p->gen, p->dev, io, *params, st, /*force_lane=*/true);
-        if (ev != hipSuccess) return hip_fail(ev, "launching the generic DLS kernel (derived visitor)");
-        return static_cast<int>(IKGPU_OK);
+        return launched(ev, "launching the generic DLS kernel (derived visitor)");
     }
     hipError_t e = p->dls_on_static_gen                      ? ikgpu::rtc_launch_generic_static(p->gen, p->gen.generic_key, io, *params, st, p->dev.queues)
                    : p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_dls_chain(p->host, p->dev, io, ikgpu::ChainJob{}, *params, st)
                    : p->host.kind == ikgpu::KernelKind::Tree ? ikgpu::launch_dls_tree(p->host, p->dev, io, *params, st)
                    : p->host.generic_build == 2              ? ikgpu::rtc_launch_generic_static(p->host, p->host.generic_key, io, *params, st, p->dev.queues)
                                                              : ikgpu::launch_dls_generic(p->host, p->dev, io, *params, st);
-    if (e != hipSuccess) return hip_fail(e, "launching the DLS kernel");
-    return static_cast<int>(IKGPU_OK);
+    return launched(e, "launching the DLS kernel");
 }
 
-// The kernel dispatch of ikgpu_evaluate_batch for validated arguments, on the problem's device, inside `guarded`.
+// The kernel dispatch of ikgpu_evaluate_batch for validated arguments, inside on_device.
 int dispatch_eval(const ikgpu_problem *p, int64_t B, const double *q, const double *targets, double *e_out, double *J_out, int layout, hipStream_t st) {
     hipError_t e = p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_eval_chain(p->host, p->dev, B, q, targets, e_out, J_out, layout, st)
                    // (a tree problem with the demo's extras -- base-relative reference, alignment row -- has its stages evaluated
@@ -729,8 +792,7 @@ int dispatch_eval(const ikgpu_problem *p, int64_t B, const double *q, const doub
                    : p->host.kind == ikgpu::KernelKind::Tree && !p->host.tree_extras()
                        ? ikgpu::launch_eval_tree(p->host, p->dev, B, q, targets, e_out, J_out, nullptr, layout, st)
                        : ikgpu::launch_eval_generic(p->gen, p->dev, B, q, targets, e_out, J_out, nullptr, layout, st);
-    if (e != hipSuccess) return hip_fail(e, "launching the evaluate kernel");
-    return static_cast<int>(IKGPU_OK);
+    return launched(e, "launching the evaluate kernel");
 }
 
 // A chain problem under the reference's own visitor has a tracking kernel: one launch for the whole sequence.
@@ -754,40 +816,72 @@ std::string variant_kernel_name(const ikgpu_problem *p, bool fused, const char *
     return p->dls_name.substr(0, lt) + suffix + (lt == std::string::npos ? "" : p->dls_name.substr(lt));
 }
 
-// The workspace of the multi-start definition run as a loop, carved in this order (each part rounded up to 256 bytes):
-// generated start [nq x B], q of the start's solve [nq x B], its error [M x B], best key [B], its iterations [B], its success flag [B].
-struct MultistartWorkspace {
-    size_t start, q, e, key, iters, success, total;
+// What the multi-start and the solution-set entry points share: K starts of each of B problems, supplied (`starts`, K - 1 slabs) or
+// drawn from `seed`, and the workspace of the definition run as a loop.
+struct StartsCall {
+    int64_t B;
+    int32_t K;
+    const double *q0, *starts;
+    uint64_t seed;
+    const double *targets;
+    const ikgpu_dls_params *params;
+    int layout;
+    void *workspace;
+    size_t workspace_bytes;
 };
-MultistartWorkspace multistart_workspace(const ikgpu_problem *p, int64_t B) {
-    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+
+// The workspace of a definition run as a loop, carved in this order (each part rounded up to 256 bytes): generated start [nq x B], q of
+// the start's solve [nq x B], its iterations [B], its success flag [B], and for the multi-start merge (with_error) its error [M x B] and
+// the best key [B].  A solution set lives in the caller's outputs.
+struct StartWorkspace {
+    size_t start, q, iters, success, e, key, total;
+};
+StartWorkspace start_workspace(const ikgpu_problem *p, int64_t B, bool with_error) {
+    size_t end = 0;
+    auto take = [&](size_t n) { const size_t at = end; end += (n + 255) / 256 * 256; return at; };
     const size_t b = static_cast<size_t>(B), nq = static_cast<size_t>(p->host.nq), M = static_cast<size_t>(p->host.rows);
-    MultistartWorkspace w{};
-    w.start = 0;
-    w.q = w.start + up(8 * nq * b);
-    w.e = w.q + up(8 * nq * b);
-    w.key = w.e + up(8 * M * b);
-    w.iters = w.key + up(8 * b);
-    w.success = w.iters + up(4 * b);
-    w.total = w.success + up(b);
+    StartWorkspace w{};
+    w.start = take(8 * nq * b);
+    w.q = take(8 * nq * b);
+    w.iters = take(4 * b);
+    w.success = take(b);
+    if (with_error) {
+        w.e = take(8 * M * b);
+        w.key = take(8 * b);
+    }
+    w.total = end;
     return w;
 }
 
-// The workspace of the solution-set definition run as a loop, carved in this order (each part rounded up to 256 bytes): generated start
-// [nq x B], q of the start's solve [nq x B], its iterations [B], its success flag [B].  The set itself lives in the caller's outputs.
-struct SolutionsWorkspace {
-    size_t start, q, iters, success, total;
-};
-SolutionsWorkspace solutions_workspace(const ikgpu_problem *p, int64_t B) {
-    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
-    const size_t b = static_cast<size_t>(B), nq = static_cast<size_t>(p->host.nq);
-    SolutionsWorkspace w{};
-    w.start = 0;
-    w.q = w.start + up(8 * nq * b);
-    w.iters = w.q + up(8 * nq * b);
-    w.success = w.iters + up(4 * b);
-    w.total = w.success + up(b);
-    return w;
+// The definition itself, start after start on the same stream: start k drawn unless supplied, solved, and handed to
+// step(k, q, ok, it, e, key) -- the solve's outputs and the merge's two arrays in the workspace -- which folds it into the caller's
+// outputs.  `what` / `query` name the definition and its workspace query in the refusal of a workspace that is too small.
+template <class Step>
+int run_starts(const ikgpu_problem *p, const StartsCall &c, const char *what, const char *query, bool with_error, hipStream_t st, Step &&step) {
+    const StartWorkspace w = start_workspace(p, c.B, with_error);
+    if (!c.workspace || c.workspace_bytes < w.total)
+        return fail(IKGPU_ERR_INVALID, std::string(what) + " workspace too small: " + std::to_string(c.workspace_bytes) + " bytes given, " +
+                                           std::to_string(w.total) + " needed (" + query + ")");
+    char *ws = static_cast<char *>(c.workspace);
+    double *start = reinterpret_cast<double *>(ws + w.start), *q = reinterpret_cast<double *>(ws + w.q), *e = with_error ? reinterpret_cast<double *>(ws + w.e) : nullptr;
+    unsigned long long *key = with_error ? reinterpret_cast<unsigned long long *>(ws + w.key) : nullptr;
+    int32_t *it = reinterpret_cast<int32_t *>(ws + w.iters);
+    uint8_t *ok = reinterpret_cast<uint8_t *>(ws + w.success);
+    const int64_t q_slab = static_cast<int64_t>(p->host.nq) * c.B;
+    for (int k = 0; k < c.K; ++k) {
+        auto named = [&](int rc) {
+            g_last_error = "start " + std::to_string(k) + ": " + g_last_error;
+            return rc;
+        };
+        const double *from = k == 0 ? c.q0 : c.starts ? c.starts + (k - 1) * q_slab : start;
+        if (k > 0 && !c.starts) {
+            const hipError_t ed = ikgpu::launch_multistart_starts(p->dev, p->host.nq, c.B, k, k + 1, c.q0, c.seed, start, c.layout, st);
+            if (ed != hipSuccess) return named(hip_fail(ed, "launching the multi-start draw"));
+        }
+        if (const int rc = dispatch_dls(p, ikgpu::BatchIO{c.B, from, c.targets, q, ok, it, c.layout}, c.params, st)) return named(rc);
+        if (const int rc = step(k, q, ok, it, e, key)) return named(rc);
+    }
+    return static_cast<int>(IKGPU_OK);
 }
 
 }  // namespace
@@ -804,25 +898,19 @@ const char *ikgpu_dls_track_kernel(const ikgpu_problem *p, const ikgpu_dls_param
 int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *targets,
                           const ikgpu_dls_params *params, double *q_traj, uint8_t *success, int32_t *iters, int layout,
                           void *stream) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (int rc = check_problem_batch(p, B)) return rc;
     if (T < 0) return fail(IKGPU_ERR_INVALID, "negative number of waypoints");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_layout(layout)) return rc;
     if (int rc = check_params(params)) return rc;
     if (B == 0 || T == 0) return IKGPU_OK;  // nothing to solve (the pointers may be null; the problem is not looked at)
-    if (!q0 || !targets || !q_traj) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B > (int64_t(1) << 31) * 32) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
+    if (!q0 || !targets || !q_traj) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
     if (T > 0x7fffffff) return fail(IKGPU_ERR_INVALID, "too many waypoints for one call");
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const hipStream_t st = static_cast<hipStream_t>(stream);
+    return on_device(p->device, stream, [&](hipStream_t st) {
         if (track_is_fused(p, params)) {
             const ikgpu::BatchIO io{B, q0, targets, q_traj, success, iters, layout};
             const ikgpu::ChainJob job{ikgpu::ChainJob::Track, static_cast<int>(T)};
-            const hipError_t e = ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st);
-            if (e != hipSuccess) return hip_fail(e, "launching the DLS tracking kernel");
-            return static_cast<int>(IKGPU_OK);
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the DLS tracking kernel");
         }
         // every other kind: the chained calls themselves, on the same stream
         const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B, t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
@@ -847,78 +935,47 @@ const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_
 
 size_t ikgpu_dls_multistart_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, const ikgpu_dls_params *params) {
     if (!p || !params || B <= 0 || K < 1 || K > 64 || multistart_fused_log2(p, params, K) >= 0) return 0;
-    return multistart_workspace(p, B).total;
+    return start_workspace(p, B, /*with_error=*/true).total;
 }
 
 int ikgpu_multistart_starts(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, uint64_t seed, double *starts_out, int layout,
                             void *stream) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (K < 1 || K > 64) return fail(IKGPU_ERR_INVALID, "the number of starts must be 1 .. 64");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_starts(K)) return rc;
+    if (int rc = check_layout(layout)) return rc;
     if (B == 0 || K == 1) return IKGPU_OK;   // start 0 is q0 itself: nothing to write
-    if (!q0 || !starts_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B > (int64_t(1) << 31) * 32 / K) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const hipError_t e = ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, 1, K, q0, seed, starts_out, layout, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return hip_fail(e, "launching the multi-start draw");
-        return static_cast<int>(IKGPU_OK);
+    if (!q0 || !starts_out) return null_argument();
+    if (int rc = check_launch_size(B, K)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        return launched(ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, 1, K, q0, seed, starts_out, layout, st), "launching the multi-start draw");
     });
 }
 
 int ikgpu_dls_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, const double *starts, uint64_t seed,
                                const double *targets, const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
                                int32_t *winner, double *err_sq, int layout, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (K < 1 || K > 64) return fail(IKGPU_ERR_INVALID, "the number of starts must be 1 .. 64");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_starts(K)) return rc;
+    if (int rc = check_layout(layout)) return rc;
     if (int rc = check_params(params)) return rc;
     if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
-    if (!q0 || !targets || !q_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B > (int64_t(1) << 31) * 32 / K) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!q0 || !targets || !q_out) return null_argument();
+    if (int rc = check_launch_size(B, K)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) {
         const int log2K = multistart_fused_log2(p, params, K);
         if (log2K >= 0) {
             const ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
             const ikgpu::ChainJob job{ikgpu::ChainJob::Multistart, 0, ikdev::MultistartArgs{starts, p->dev.draw, seed, winner, err_sq, log2K}};
-            const hipError_t e = ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st);
-            if (e != hipSuccess) return hip_fail(e, "launching the multi-start DLS kernel");
-            return static_cast<int>(IKGPU_OK);
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the multi-start DLS kernel");
         }
-        // every other case: the definition itself, start after start on the same stream, merged into the caller's outputs
-        const MultistartWorkspace w = multistart_workspace(p, B);
-        if (!workspace || workspace_bytes < w.total)
-            return fail(IKGPU_ERR_INVALID, "multi-start workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                               std::to_string(w.total) + " needed (ikgpu_dls_multistart_workspace_bytes)");
-        char *ws = static_cast<char *>(workspace);
-        double *start = reinterpret_cast<double *>(ws + w.start), *q = reinterpret_cast<double *>(ws + w.q), *e = reinterpret_cast<double *>(ws + w.e);
-        unsigned long long *key = reinterpret_cast<unsigned long long *>(ws + w.key);
-        int32_t *it = reinterpret_cast<int32_t *>(ws + w.iters);
-        uint8_t *ok = reinterpret_cast<uint8_t *>(ws + w.success);
-        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B;
-        for (int k = 0; k < K; ++k) {
-            auto named = [&](int rc) {
-                g_last_error = "start " + std::to_string(k) + ": " + g_last_error;
-                return rc;
-            };
-            const double *from = k == 0 ? q0 : starts ? starts + (k - 1) * q_slab : start;
-            if (k > 0 && !starts) {
-                const hipError_t ed = ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, k, k + 1, q0, seed, start, layout, st);
-                if (ed != hipSuccess) return named(hip_fail(ed, "launching the multi-start draw"));
-            }
-            if (const int rc = dispatch_dls(p, ikgpu::BatchIO{B, from, targets, q, ok, it, layout}, params, st)) return named(rc);
-            if (const int rc = dispatch_eval(p, B, q, targets, e, nullptr, layout, st)) return named(rc);
-            const ikgpu::MultistartMerge m{B, p->host.nq, p->host.rows, layout, k, q, e, ok, it, key, q_out, success, iters, winner, err_sq};
-            const hipError_t em = ikgpu::launch_multistart_merge(m, st);
-            if (em != hipSuccess) return named(hip_fail(em, "launching the multi-start merge"));
-        }
-        return static_cast<int>(IKGPU_OK);
+        // every other case: the definition itself, each start merged into the caller's outputs
+        const StartsCall c{B, K, q0, starts, seed, targets, params, layout, workspace, workspace_bytes};
+        return run_starts(p, c, "multi-start", "ikgpu_dls_multistart_workspace_bytes", /*with_error=*/true, st,
+                          [&](int k, double *q, uint8_t *ok, int32_t *it, double *e, unsigned long long *key) {
+                              if (const int rc = dispatch_eval(p, B, q, targets, e, nullptr, layout, st)) return rc;
+                              const ikgpu::MultistartMerge m{B, p->host.nq, p->host.rows, layout, k, q, e, ok, it, key, q_out, success, iters, winner, err_sq};
+                              return launched(ikgpu::launch_multistart_merge(m, st), "launching the multi-start merge");
+                          });
     });
 }
 
@@ -931,79 +988,52 @@ const char *ikgpu_dls_solutions_kernel(const ikgpu_problem *p, const ikgpu_dls_p
 
 size_t ikgpu_dls_solutions_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, int32_t N, const ikgpu_dls_params *params) {
     if (!p || !params || B <= 0 || K < 1 || K > 64 || N < 1 || N > K || multistart_fused_log2(p, params, K) >= 0) return 0;
-    return solutions_workspace(p, B).total;
+    return start_workspace(p, B, /*with_error=*/false).total;
 }
 
 int ikgpu_dls_solutions_batch(const ikgpu_problem *p, int64_t B, int32_t K, int32_t N, const double *q0, const double *starts, uint64_t seed,
                               const double *targets, const ikgpu_dls_params *params, double sep, double *q_sols, int32_t *count,
                               int32_t *which, int32_t *iters, int layout, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (K < 1 || K > 64) return fail(IKGPU_ERR_INVALID, "the number of starts must be 1 .. 64");
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_starts(K)) return rc;
     if (N < 1 || N > K) return fail(IKGPU_ERR_INVALID, "the number of solutions kept must be 1 .. the number of starts");
     if (!(sep >= 0.0) || !std::isfinite(sep)) return fail(IKGPU_ERR_INVALID, "the separation must be finite and not negative");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_layout(layout)) return rc;
     if (int rc = check_params(params)) return rc;
     if (params->stop_sq_tol < 0.0 && !ikgpu::visitor_extended(*params))
         return fail(IKGPU_ERR_INVALID, "the never-stop visitor has no converged start: a solution set needs a stop rule (stop_sq_tol >= 0)");
     if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
-    if (!q0 || !targets || !q_sols || !count) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B > (int64_t(1) << 31) * 32 / K) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!q0 || !targets || !q_sols || !count) return null_argument();
+    if (int rc = check_launch_size(B, K)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) {
         const int log2K = multistart_fused_log2(p, params, K);
         if (log2K >= 0) {
             const ikgpu::BatchIO io{B, q0, targets, q_sols, nullptr, iters, layout};
             ikgpu::ChainJob job{};
             job.kind = ikgpu::ChainJob::Solutions;
             job.sol = ikdev::SolutionsArgs{ikdev::MultistartArgs{starts, p->dev.draw, seed, nullptr, nullptr, log2K}, count, which, sep, N};
-            const hipError_t e = ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st);
-            if (e != hipSuccess) return hip_fail(e, "launching the solution-set DLS kernel");
-            return static_cast<int>(IKGPU_OK);
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the solution-set DLS kernel");
         }
-        // every other case: the definition itself, start after start on the same stream, inserted into the caller's outputs
-        const SolutionsWorkspace w = solutions_workspace(p, B);
-        if (!workspace || workspace_bytes < w.total)
-            return fail(IKGPU_ERR_INVALID, "solution-set workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                               std::to_string(w.total) + " needed (ikgpu_dls_solutions_workspace_bytes)");
-        char *ws = static_cast<char *>(workspace);
-        double *start = reinterpret_cast<double *>(ws + w.start), *q = reinterpret_cast<double *>(ws + w.q);
-        int32_t *it = reinterpret_cast<int32_t *>(ws + w.iters);
-        uint8_t *ok = reinterpret_cast<uint8_t *>(ws + w.success);
-        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B;
-        for (int k = 0; k < K; ++k) {
-            auto named = [&](int rc) {
-                g_last_error = "start " + std::to_string(k) + ": " + g_last_error;
-                return rc;
-            };
-            const double *from = k == 0 ? q0 : starts ? starts + (k - 1) * q_slab : start;
-            if (k > 0 && !starts) {
-                const hipError_t ed = ikgpu::launch_multistart_starts(p->dev, p->host.nq, B, k, k + 1, q0, seed, start, layout, st);
-                if (ed != hipSuccess) return named(hip_fail(ed, "launching the multi-start draw"));
-            }
-            if (const int rc = dispatch_dls(p, ikgpu::BatchIO{B, from, targets, q, ok, it, layout}, params, st)) return named(rc);
-            const ikgpu::SolutionsInsert m{B, p->host.nq, layout, k, N, sep, p->dev.q_in_chain, q, ok, it, q_sols, count, which, iters};
-            const hipError_t em = ikgpu::launch_solutions_insert(m, st);
-            if (em != hipSuccess) return named(hip_fail(em, "launching the solution-set insert"));
-        }
-        return static_cast<int>(IKGPU_OK);
+        // every other case: the definition itself, each start inserted into the caller's outputs
+        const StartsCall c{B, K, q0, starts, seed, targets, params, layout, workspace, workspace_bytes};
+        return run_starts(p, c, "solution-set", "ikgpu_dls_solutions_workspace_bytes", /*with_error=*/false, st,
+                          [&](int k, double *q, uint8_t *ok, int32_t *it, double *, unsigned long long *) {
+                              const ikgpu::SolutionsInsert m{B, p->host.nq, layout, k, N, sep, p->dev.q_in_chain, q, ok, it, q_sols, count, which, iters};
+                              return launched(ikgpu::launch_solutions_insert(m, st), "launching the solution-set insert");
+                          });
     });
 }
 
 int ikgpu_dls_solve_batch_host(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets,
                                const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
                                int layout) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (int rc = check_problem_batch(p, B)) return rc;
     if (int rc = check_params(params)) return rc;
     if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null)
-    if (!q0 || !targets || !q_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    const int lay = layout & ~IKGPU_TARGETS_POSE7;
-    if (lay != IKGPU_SOA && lay != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (!q0 || !targets || !q_out) return null_argument();
+    if (int rc = check_host_layout(layout)) return rc;
     return host_solve(p, B, q0, targets, q_out, success, iters, layout, [&](int64_t Bk, const double *d_q0, const double *d_t, double *d_q, uint8_t *d_s, int32_t *d_i, hipStream_t st) {
-        return ikgpu_dls_solve_batch(p, Bk, d_q0, d_t, params, d_q, d_s, d_i, lay, st);
+        return ikgpu_dls_solve_batch(p, Bk, d_q0, d_t, params, d_q, d_s, d_i, layout & ~IKGPU_TARGETS_POSE7, st);
     });
 }
 
@@ -1021,109 +1051,82 @@ const char *ikgpu_pik_kernel(const ikgpu_problem *p, const ikgpu_pik_params *par
     if (!p || !params) return "";
     if (pik_is_one_dls_level(p, params)) return p->dls_name.c_str();
     if (pik_is_two_levels_on_the_tree(p, params)) return p->pik_tree_name.c_str();
-    if (pik_runs_static(p, params)) {
-        if (p->pik_static_name.empty()) p->pik_static_name = p->pik_name.substr(0, p->pik_name.size() - 1) + ",static>";
-        return p->pik_static_name.c_str();
-    }
-    return p->pik_name.c_str();
+    return pik_runs_static(p, params) ? p->pik_static_name.c_str() : p->pik_name.c_str();
 }
 
 int ikgpu_pik_solve_batch(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets,
                           const ikgpu_pik_params *params, double *q_out, uint8_t *success, int32_t *iters, int layout,
                           void *stream) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_layout(layout)) return rc;
     if (int rc = check_pik_params(p, params)) return rc;
     if (B == 0) return IKGPU_OK;
-    if (!q0 || !targets || !q_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B > (int64_t(1) << 31) * 32) return fail(IKGPU_ERR_INVALID, "batch too large for one launch");
+    if (!q0 || !targets || !q_out) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
     if (pik_is_one_dls_level(p, params)) {
-        ikgpu_dls_params d{};   // (the derived-visitor members stay off)
-        d.max_iterations = params->max_iterations; d.damping = params->lambda[0]; d.step_length = params->step_length; d.stop_sq_tol = params->stop_sq_tol;
+        const ikgpu_dls_params d = pik_level0_as_dls(params);
         return ikgpu_dls_solve_batch(p, B, q0, targets, &d, q_out, success, iters, layout, stream);
     }
-    if (pik_is_two_levels_on_the_tree(p, params)) {
-        return guarded([&] {
-            DeviceGuard g(p->device);
-            if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-            ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
-            ikgpu_dls_params d{};
-            d.max_iterations = params->max_iterations; d.damping = params->lambda[0]; d.step_length = params->step_length; d.stop_sq_tol = params->stop_sq_tol;
-            const hipError_t e = ikgpu::launch_dls_tree(p->host, p->dev, io, d, static_cast<hipStream_t>(stream), &params->lambda[1]);
-            if (e != hipSuccess) return hip_fail(e, "launching the tree kernel (two-level ik::pik)");
-            return static_cast<int>(IKGPU_OK);
+    const ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
+    if (pik_is_two_levels_on_the_tree(p, params))
+        return on_device(p->device, stream, [&](hipStream_t st) {
+            return launched(ikgpu::launch_dls_tree(p->host, p->dev, io, pik_level0_as_dls(params), st, &params->lambda[1]),
+                            "launching the tree kernel (two-level ik::pik)");
         });
-    }
     const bool on_static = pik_runs_static(p, params);
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
-        bool has_da = false;
-        if (params->da)
-            for (int k = 0; k < p->gen.nv; ++k) has_da = has_da || params->da[k] != 0.0;
-        const hipError_t e = on_static ? ikgpu::rtc_launch_pik_static(p->gen, p->pik_static_key[has_da ? 1 : 0], io, *params, static_cast<hipStream_t>(stream))
-                                       : ikgpu::launch_pik_generic(p->gen, p->dev, io, *params, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return hip_fail(e, "launching the PIK kernel");
-        return static_cast<int>(IKGPU_OK);
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        return launched(on_static ? ikgpu::rtc_launch_pik_static(p->gen, p->pik_static_key[pik_has_da(p, params) ? 1 : 0], io, *params, st)
+                                  : ikgpu::launch_pik_generic(p->gen, p->dev, io, *params, st),
+                        "launching the PIK kernel");
     });
 }
 
 int ikgpu_pik_solve_batch_host(const ikgpu_problem *p, int64_t B, const double *q0, const double *targets,
                                const ikgpu_pik_params *params, double *q_out, uint8_t *success, int32_t *iters,
                                int layout) {
-    if (!p) return fail(IKGPU_ERR_INVALID, "null problem");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
+    if (int rc = check_problem_batch(p, B)) return rc;
     if (int rc = check_pik_params(p, params)) return rc;
     if (B == 0) return IKGPU_OK;
-    if (!q0 || !targets || !q_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    const int lay = layout & ~IKGPU_TARGETS_POSE7;
-    if (lay != IKGPU_SOA && lay != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (!q0 || !targets || !q_out) return null_argument();
+    if (int rc = check_host_layout(layout)) return rc;
     return host_solve(p, B, q0, targets, q_out, success, iters, layout, [&](int64_t Bk, const double *d_q0, const double *d_t, double *d_q, uint8_t *d_s, int32_t *d_i, hipStream_t st) {
-        return ikgpu_pik_solve_batch(p, Bk, d_q0, d_t, params, d_q, d_s, d_i, lay, st);
+        return ikgpu_pik_solve_batch(p, Bk, d_q0, d_t, params, d_q, d_s, d_i, layout & ~IKGPU_TARGETS_POSE7, st);
     });
 }
 
+// (no problem, so no device to select: the launch runs on the caller's current device)
 int ikgpu_targets_from_pose7(int64_t B, int32_t ntasks, const double *pose7, double *targets12, int layout, void *stream) {
-    if (!pose7 || !targets12) return fail(IKGPU_ERR_INVALID, "null argument");
+    if (!pose7 || !targets12) return null_argument();
     if (B < 0 || ntasks < 0) return fail(IKGPU_ERR_INVALID, "negative size");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (int rc = check_layout(layout)) return rc;
     if (B == 0 || ntasks == 0) return IKGPU_OK;
-    const hipError_t e = ikgpu::launch_targets_from_pose7(B, ntasks, pose7, targets12, layout, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "launching the target expansion kernel");
-    return IKGPU_OK;
+    return guarded([&] {
+        return launched(ikgpu::launch_targets_from_pose7(B, ntasks, pose7, targets12, layout, static_cast<hipStream_t>(stream)),
+                        "launching the target expansion kernel");
+    });
 }
 
 int ikgpu_evaluate_batch(const ikgpu_problem *p, int64_t B, const double *q, const double *targets, double *e_out,
                          double *J_out, int layout, void *stream) {
-    if (!p || !q || !targets || !e_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (!p || !q || !targets || !e_out) return null_argument();
+    if (int rc = check_batch(B)) return rc;
+    if (int rc = check_layout(layout)) return rc;
     if (B == 0) return IKGPU_OK;
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        return dispatch_eval(p, B, q, targets, e_out, J_out, layout, static_cast<hipStream_t>(stream));
-    });
+    return on_device(p->device, stream, [&](hipStream_t st) { return dispatch_eval(p, B, q, targets, e_out, J_out, layout, st); });
 }
 
 int ikgpu_task_frames_fk_batch(const ikgpu_problem *p, int64_t B, const double *q, double *oMf_out, int layout,
                                void *stream) {
-    if (!p || !q || !oMf_out) return fail(IKGPU_ERR_INVALID, "null argument");
-    if (B < 0) return fail(IKGPU_ERR_INVALID, "negative batch size");
-    if (layout != IKGPU_SOA && layout != IKGPU_AOS) return fail(IKGPU_ERR_INVALID, "unknown layout");
+    if (!p || !q || !oMf_out) return null_argument();
+    if (int rc = check_batch(B)) return rc;
+    if (int rc = check_layout(layout)) return rc;
     if (B == 0) return IKGPU_OK;
-    return guarded([&] {
-        DeviceGuard g(p->device);
-        if (!g.ok) return fail(IKGPU_ERR_DEVICE, "hipSetDevice failed");
-        const hipStream_t st = static_cast<hipStream_t>(stream);
+    return on_device(p->device, stream, [&](hipStream_t st) {
         hipError_t e = p->host.kind == ikgpu::KernelKind::Chain  ? ikgpu::launch_fk_chain(p->host, p->dev, B, q, oMf_out, layout, st)
                        : p->host.kind == ikgpu::KernelKind::Tree && !p->host.tree_extras()
                            ? ikgpu::launch_eval_tree(p->host, p->dev, B, q, q, nullptr, nullptr, oMf_out, layout, st)
                            : ikgpu::launch_eval_generic(p->gen, p->dev, B, q, q, nullptr, nullptr, oMf_out, layout, st);
-        if (e != hipSuccess) return hip_fail(e, "launching the FK kernel");
-        return static_cast<int>(IKGPU_OK);
+        return launched(e, "launching the FK kernel");
     });
 }
 
