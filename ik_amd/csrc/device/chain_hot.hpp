@@ -258,7 +258,7 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
     }
     LogAndJlog lj;
     double Cm[9];
-    log6_and_jlog6_hot<false>(Re, pe, lj, &Cm);
+    log6_and_jlog6_hot<false, true>(Re, pe, lj, &Cm);
 #pragma unroll
     for (int i = 0; i < 6; ++i) e[i] = lj.e[i];
 
@@ -383,7 +383,7 @@ IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const 
         double G[M * M];
         hot_gram<NJ, S>(col, prm.lam2, G);
         double y[M];
-        chol_solve<M>(G, e, y);
+        ldlt_solve<M>(G, e, y);
 
         if (!NEVERSTOP) {
             double e0sq = 0.0;
@@ -408,23 +408,29 @@ IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const 
 // store that might alias it) cost one HBM round trip per entry -- nine for a Cassie leg, ~10 us of a 150 us launch.
 template <int NJ>
 IKD_FN void hot_pass_through_from(const ChainKernelArgs<NJ> &a, const double *q_src, double *q_out, int64_t b, bool stepped) {
+    const ChainStrides st = chain_strides(a);
     constexpr int kGroup = 16;   // (a Cassie model's sixteen entries in ONE pass: with groups of eight the second group's loads waited
                                  // for the first group's stores -- a second HBM round trip in the prologue)
     for (int i0 = 0; i0 < a.nq; i0 += kGroup) {
         double v[kGroup], lo[kGroup], hi[kGroup];
         bool out[kGroup];
+        // (the wave-uniform reads in one batch, ahead of the per-lane loads: interleaved, each entry's three sat between two of those)
 #pragma unroll
         for (int k = 0; k < kGroup; ++k) {
             const int i = i0 + k < a.nq ? i0 + k : a.nq - 1;
             out[k] = i0 + k < a.nq && !a.q_in_chain[i];
-            v[k] = q_src[at(a.layout, a.B, a.nq, i, b)];
             lo[k] = a.lower[i];
             hi[k] = a.upper[i];
         }
 #pragma unroll
         for (int k = 0; k < kGroup; ++k) {
+            const int i = i0 + k < a.nq ? i0 + k : a.nq - 1;
+            v[k] = q_src[at(st.elem, st.q_prob, i, b)];
+        }
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) {
             const double c = dmin(hi[k], dmax(v[k], lo[k]));
-            if (out[k]) q_out[at(a.layout, a.B, a.nq, i0 + k, b)] = stepped ? c : v[k];
+            if (out[k]) q_out[at(st.elem, st.q_prob, i0 + k, b)] = stepped ? c : v[k];
         }
     }
 }
@@ -444,7 +450,7 @@ __device__ __forceinline__ void hot_refill_body(const ChainKernelArgs<NJ> &a, co
         double G[M * M];
         hot_gram<NJ, S>(col, a.prm.lam2, G);
         double y[M];
-        chol_solve<M>(G, e, y);
+        ldlt_solve<M>(G, e, y);
         double e0sq = 0.0;
         if (a.prm.priority == 0) {
 #pragma unroll
@@ -460,6 +466,7 @@ __device__ __forceinline__ void hot_refill_body(const ChainKernelArgs<NJ> &a, co
 // B independent ik::dls() calls, lane `gid`: load, solve, store -- dls_chain_body (chain_kernel_body.hpp) with the hot program.
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
 IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
 #if defined(IKGPU_HOT_STAMP) && IKD_ON_DEVICE
     const long long rs = wall_clock64();   // wave start, 100 MHz ticks
 #endif
@@ -467,7 +474,7 @@ IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t g
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
     double q[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
     double oMt[12];
     load_target(a, b, oMt);
     // The visitor never stops: every lane takes max_iterations steps, so what happens to the entries outside the support is
@@ -491,7 +498,7 @@ IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t g
         append_unfinished(a.append_list, a.append_count, valid && !success && iters < a.prm.max_iterations, b);
     if (!valid) return;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) a.q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+    for (int j = 0; j < NJ; ++j) a.q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
     if (!NEVERSTOP) hot_pass_through(a, b, iters > 0);
     if (a.success) a.success[b] = success ? 1 : 0;
 #if defined(IKGPU_HOT_STAMP) && IKD_ON_DEVICE
@@ -514,12 +521,13 @@ IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t g
 // is in flight during the iteration loop of waypoint k and composed after it: twelve doubles parked, nothing of them in the loop.
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
 IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
     const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
     double q[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
     // Order per waypoint: solve k, compose target k + 1 (its loads were issued before solve k began), store slab k, THEN issue the loads
     // of target k + 2.  The wait that consumes a prefetched target therefore never has a store of this waypoint in front of it (loads
     // and stores share one counter on gfx950: behind a store the wait would be for the store's acknowledgement, once per waypoint).
@@ -540,7 +548,7 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
         if (k + 1 < T) compose_target(a, next, oMt);
         if (valid) {
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+            for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
             if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
             if (a.iters) a.iters[k * a.B + b] = iters;
             if (!NEVERSTOP) hot_pass_through_to(a, q_out, b, stepped);

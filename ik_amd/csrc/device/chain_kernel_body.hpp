@@ -66,12 +66,39 @@ IKD_FN int64_t at(int layout, int64_t B, int ncomp, int c, int64_t b) {
     return layout == LAYOUT_SOA ? static_cast<int64_t>(c) * B + b : b * ncomp + c;
 }
 
+// The same place through two strides, for the chain bodies: the layout is resolved ONCE per body into an element stride and a problem
+// stride (SOA: B and 1; AOS: 1 and the number of components -- nq for q0 / q_out / starts, 12 for the targets), and entry c of problem
+// b is one multiply-add away.  at() above chooses per access, and on a wave-uniform layout hipcc made a scalar BRANCH of every such
+// choice: ~180 conditional branches (45-60 cycles each for a lone wave when taken) and as many flow blocks with a wait in front in the
+// prologue of the hot kernels.  The strides are derived here, on the device, from the `layout` the launchers have always filled in --
+// not carried in the kernel arguments: the host-side lane emulators under tests/ fill ChainKernelArgs themselves.  They are made
+// opaque to the optimiser (IKD_OPAQUE_S) so that it cannot fold the multiply back into the choice.
+struct ChainStrides {
+    int64_t elem, q_prob, t_prob;
+};
+#if IKD_ON_DEVICE
+#define IKD_OPAQUE_S(x) asm("" : "+s"(x))   // (not volatile: two bodies inlined into one kernel may share the values)
+#else
+#define IKD_OPAQUE_S(x) ((void)0)
+#endif
+template <class Args>
+IKD_FN ChainStrides chain_strides(const Args &a) {
+    const bool soa = a.layout == LAYOUT_SOA;
+    ChainStrides s{soa ? a.B : int64_t{1}, soa ? int64_t{1} : static_cast<int64_t>(a.nq), soa ? int64_t{1} : int64_t{12}};
+    IKD_OPAQUE_S(s.elem);
+    IKD_OPAQUE_S(s.q_prob);
+    IKD_OPAQUE_S(s.t_prob);
+    return s;
+}
+IKD_FN int64_t at(int64_t elem, int64_t prob, int c, int64_t b) { return static_cast<int64_t>(c) * elem + b * prob; }
+
 // oMt = oMr * target (reference ik/ik/frame.hpp:48); oMr is constant for a world-fixed reference.
 template <int NJ>
 IKD_FN void load_target(const ChainKernelArgs<NJ> &a, int64_t b, double (&oMt)[12]) {
+    const ChainStrides st = chain_strides(a);
     double t[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) t[k] = a.targets[at(a.layout, a.B, 12, k, b)];
+    for (int k = 0; k < 12; ++k) t[k] = a.targets[at(st.elem, st.t_prob, k, b)];
     const double *r = a.ref_pl;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -85,12 +112,13 @@ IKD_FN void load_target(const ChainKernelArgs<NJ> &a, int64_t b, double (&oMt)[1
 // B independent ik::dls() calls (reference ik/ik/dls.cpp:5-78), lane `gid`.
 template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
 IKD_FN void dls_chain_body(const ChainKernelArgs<NJ> &a, const Desc &d, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
 
     double q[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
     double oMt[12];
     load_target(a, b, oMt);
 
@@ -102,14 +130,14 @@ IKD_FN void dls_chain_body(const ChainKernelArgs<NJ> &a, const Desc &d, int64_t 
     if (a.append_count) append_unfinished(a.append_list, a.append_count, valid && !success && iters < a.prm.max_iterations, b);
     if (!valid) return;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) a.q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+    for (int j = 0; j < NJ; ++j) a.q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
     // Entries outside the task support: dq = 0 there, so the loop only ever clamps them
     // (reference ik/ik/dls.cpp:71 clips the whole q after each step; no step is taken when iters == 0).
     for (int i = 0; i < a.nq; ++i) {
         if (a.q_in_chain[i]) continue;
-        const double v = a.q0[at(a.layout, a.B, a.nq, i, b)];
+        const double v = a.q0[at(st.elem, st.q_prob, i, b)];
         const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-        a.q_out[at(a.layout, a.B, a.nq, i, b)] = (iters > 0) ? c : v;
+        a.q_out[at(st.elem, st.q_prob, i, b)] = (iters > 0) ? c : v;
     }
     if (a.success) a.success[b] = success ? 1 : 0;
     if (a.iters) a.iters[b] = iters;
@@ -123,8 +151,9 @@ IKD_FN void dls_chain_body(const ChainKernelArgs<NJ> &a, const Desc &d, int64_t 
 // consumed after it: the same expressions, the same bits.
 template <int NJ>
 IKD_FN void load_target_raw(const ChainKernelArgs<NJ> &a, const double *targets, int64_t b, double (&t)[12]) {
+    const ChainStrides st = chain_strides(a);
 #pragma unroll
-    for (int k = 0; k < 12; ++k) t[k] = targets[at(a.layout, a.B, 12, k, b)];
+    for (int k = 0; k < 12; ++k) t[k] = targets[at(st.elem, st.t_prob, k, b)];
 }
 template <int NJ>
 IKD_FN void compose_target(const ChainKernelArgs<NJ> &a, const double (&t)[12], double (&oMt)[12]) {
@@ -144,13 +173,14 @@ IKD_FN void compose_target(const ChainKernelArgs<NJ> &a, const double (&t)[12], 
 // stepped ? clip(q0[i]) : q0[i] with stepped = "some waypoint <= k took a step" -- read from q0 only, never from an earlier slab.
 template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
 IKD_FN void dls_chain_track_body(const ChainKernelArgs<NJ> &a, const Desc &d, int T, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
     const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
 
     double q[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
     // (order per waypoint: solve k, compose target k + 1, store slab k, issue the loads of target k + 2 -- see hot_track_body)
     double next[12], oMt[12];
     if (T > 0) {
@@ -168,14 +198,14 @@ IKD_FN void dls_chain_track_body(const ChainKernelArgs<NJ> &a, const Desc &d, in
         if (valid) {
             double *q_out = a.q_out + k * q_slab;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+            for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
             if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
             if (a.iters) a.iters[k * a.B + b] = iters;
             for (int i = 0; i < a.nq; ++i) {
                 if (a.q_in_chain[i]) continue;
-                const double v = a.q0[at(a.layout, a.B, a.nq, i, b)];
+                const double v = a.q0[at(st.elem, st.q_prob, i, b)];
                 const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-                q_out[at(a.layout, a.B, a.nq, i, b)] = stepped ? c : v;
+                q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
             }
         }
         if (k + 2 < T) load_target_raw(a, a.targets + (k + 2) * t_slab, b, next);
@@ -198,12 +228,13 @@ IKD_FN const double *multistart_source(const ChainKernelArgs<NJ> &a, const Multi
 // The chain entries of start k of problem b.
 template <int NJ>
 IKD_FN void multistart_load(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, int64_t b, int k, double (&q)[NJ]) {
+    const ChainStrides st = chain_strides(a);
     const double *src = multistart_source(a, ms, k);
     const bool generated = k > 0 && !ms.starts;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int i = a.qidx[j];
-        const double v = src[at(a.layout, a.B, a.nq, i, b)];
+        const double v = src[at(st.elem, st.q_prob, i, b)];
         const double r = multistart_draw(ms.seed, b, k, i, a.lower[i], a.upper[i]);
         q[j] = (generated && ms.draw[i]) ? r : v;
     }
@@ -230,8 +261,9 @@ IKD_FN void dls_chain_multistart_lane(const ChainKernelArgs<NJ> &a, const Multis
 template <int NJ, class Pass>
 IKD_FN void multistart_store(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, int64_t b, int k, const double (&q)[NJ], bool success,
                              int iters, double err_sq, Pass pass) {
+    const ChainStrides st = chain_strides(a);
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) a.q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+    for (int j = 0; j < NJ; ++j) a.q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
     pass(multistart_source(a, ms, k), iters > 0);
     if (a.success) a.success[b] = success ? 1 : 0;
     if (a.iters) a.iters[b] = iters;
@@ -242,11 +274,12 @@ IKD_FN void multistart_store(const ChainKernelArgs<NJ> &a, const MultistartArgs 
 // Entries outside the task support of a solve started from column b of `src`: clipped once a step was taken (dls_chain_body).
 template <int NJ>
 IKD_FN void chain_pass_through_from(const ChainKernelArgs<NJ> &a, const double *src, int64_t b, bool stepped) {
+    const ChainStrides st = chain_strides(a);
     for (int i = 0; i < a.nq; ++i) {
         if (a.q_in_chain[i]) continue;
-        const double v = src[at(a.layout, a.B, a.nq, i, b)];
+        const double v = src[at(st.elem, st.q_prob, i, b)];
         const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-        a.q_out[at(a.layout, a.B, a.nq, i, b)] = stepped ? c : v;
+        a.q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
     }
 }
 
@@ -275,11 +308,12 @@ IKD_FN void dls_chain_multistart_body(const ChainKernelArgs<NJ> &a, const Multis
 // Entries outside the task support of a solve started from column b of `src`, into a slab of its own (chain_pass_through_from).
 template <int NJ>
 IKD_FN void chain_pass_through_into(const ChainKernelArgs<NJ> &a, const double *src, double *q_out, int64_t b, bool stepped) {
+    const ChainStrides st = chain_strides(a);
     for (int i = 0; i < a.nq; ++i) {
         if (a.q_in_chain[i]) continue;
-        const double v = src[at(a.layout, a.B, a.nq, i, b)];
+        const double v = src[at(st.elem, st.q_prob, i, b)];
         const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-        q_out[at(a.layout, a.B, a.nq, i, b)] = stepped ? c : v;
+        q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
     }
 }
 
@@ -300,10 +334,11 @@ IKD_FN void dls_chain_solutions_lane(const ChainKernelArgs<NJ> &a, const Solutio
 template <int NJ, class Pass>
 IKD_FN void solutions_store(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, int64_t b, int k, int slot, const double (&q)[NJ], int iters,
                             Pass pass) {
+    const ChainStrides st = chain_strides(a);
     double *q_out = a.q_out + static_cast<int64_t>(slot) * a.nq * a.B;
     pass(multistart_source(a, sa.ms, k), q_out, iters > 0);
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+    for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
     if (sa.which) sa.which[slot * a.B + b] = k;
     if (a.iters) a.iters[slot * a.B + b] = iters;
 }
@@ -343,6 +378,7 @@ IKD_FN void dls_chain_solutions_body(const ChainKernelArgs<NJ> &a, const Solutio
 // iterate(q, oMt, have) runs ONE iteration of this lane's problem in place and returns "the visitor stopped it before the step".
 template <int NJ, class IterFn>
 __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, unsigned long long *queue, int chunk_and_batch, IterFn iterate) {
+    const ChainStrides st = chain_strides(a);
     const int lane = static_cast<int>(threadIdx.x) & 63;                 // one wave per workgroup
     const int64_t first_round = static_cast<int64_t>(gridDim.x) * 64;
     // work items: the batch's problems, or (second phase) the entries of the worklist; `b` is always a PROBLEM index
@@ -363,7 +399,7 @@ __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, 
     if (static_cast<int64_t>(blockIdx.x) >= working) return;
     b = problem(have ? w0 : 0);                                          // idle lanes shadow a valid problem
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+    for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(st.elem, st.q_prob, a.qidx[j], b)];
     load_target(a, b, oMt);
     if (listed) it = a.iters[b];                                         // (the iterations the first phase took over this problem)
     // The wave's own reserve [pool_lo, pool_hi) of unsolved problems (wave-uniform): finished lanes are served from it, and only when
@@ -383,7 +419,7 @@ __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, 
         const bool done = have && (stop_now || it >= max_it);
         if (done) {
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) a.q_out[at(a.layout, a.B, a.nq, a.qidx[j], b)] = q[j];
+            for (int j = 0; j < NJ; ++j) a.q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
             if (a.success) a.success[b] = stop_now ? 1 : 0;
             a.iters[b] = stop_now ? it - 1 : max_it;                     // never null here: the pass-through kernel reads it
             have = false;
@@ -413,7 +449,7 @@ __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, 
                 have = true;
                 b = problem(nb);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+                for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(st.elem, st.q_prob, a.qidx[j], b)];
                 load_target(a, b, oMt);
                 it = listed ? a.iters[b] : 0;
             }

@@ -212,7 +212,7 @@ IKD_FN bool chain_iteration(const Desc &d, const LoopParams &prm, double (&q)[NJ
             G[a * M + b] = s;
         }
     double y[M];
-    chol_solve<M>(G, e, y);
+    ldlt_solve<M>(G, e, y);
 
     double e0sq = 0.0;
     if (prm.priority == 0) {

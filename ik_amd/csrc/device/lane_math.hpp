@@ -479,7 +479,12 @@ IKD_FN void log6_and_jlog6_inv(const double (&Re)[9], const double (&pe)[3], Log
 // Four FP64 transcendentals (16 cycles of issue each) instead of seven.  Results differ from the other front end by rounding only.
 // WITH_BM = false: o.Bm is left unset and C is returned instead -- a caller that goes on to multiply by the frame rotation forms
 // (C A) Rf^T as C (A Rf^T) and saves the 27 multiply-adds of C A (device/chain_hot.hpp).
-template <bool WITH_BM = true>
+// LEAN (the hot chain program, device/chain_hot.hpp): the same four transcendentals spent otherwise -- 1/h = rsqrt(z (1 - z)) with
+// h = z (1 - z) / h (no square root of its own, no product theta h in front of the reciprocal) and 1/theta a reciprocal of its own;
+// the symmetric part of Jlog3 once per pair, its diagonal term shared with alpha: 14 issue slots fewer in the hot loops.  The tree
+// program keeps the form it was tuned with: at 491 of 512 registers the shorter form allocated worse (tools/kernel_stats.py: 5719 ->
+// 5731 issue slots, 28 -> 35 v_mov_b64).  The two differ by rounding only (tests/test_log6_scalars_host.py holds LEAN to the oracle).
+template <bool WITH_BM = true, bool LEAN = false>
 IKD_FN void log6_and_jlog6_hot(const double (&Re)[9], const double (&pe)[3], LogAndJlog &o, double (*Cout)[9] = nullptr) {
     constexpr double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
     constexpr double pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01,
@@ -497,7 +502,8 @@ IKD_FN void log6_and_jlog6_hot(const double (&Re)[9], const double (&pe)[3], Log
     // (1 + cos theta)/2 = cos^2(theta/2) = 1 - z, kept off zero: at theta = pi to rounding (trace <= -1: x clamps to -1) an exact 0
     // would make h = 0 below, and the ONE reciprocal r = 1 / (theta h) would return 1/theta = r h = 0 -- beta, Jlog3's diagonal and the
     // translation of log6 all wrong, a step off by a radian (found by the step-synchronised parity test on its tenth seed: one lane-step
-    // in 3e7).  With the floor h = 2^-52, r = 1.4e15, r h = 1/pi, and cot = zc / h = 2^-52 stands in for 0.
+    // in 3e7).  With the floor h = 2^-52, r = 1.4e15, r h = 1/pi, and cot = zc / h = 2^-52 stands in for 0.  LEAN keeps these values:
+    // z zc = 2^-104, 1/h = 2^52, h = 2^-52, cot = 2^-52, and 1/theta = 1/pi from its own reciprocal.
     const double zc = dmax(dfma(0.5, x, 0.5), 0x1p-104);
     const double za = mid ? x * x : dfma(-0.5, ax, 0.5);
     double pp_ = dfma3(za, pS5, pS4);
@@ -518,9 +524,23 @@ IKD_FN void log6_and_jlog6_hot(const double (&Re)[9], const double (&pe)[3], Log
     const double res_out = dfma(pos ? 2.0 : -2.0, tl, pos ? 0.0 : kPi);
     const double theta = mid ? res_mid : res_out;
     // ---- the scalars of log3 / log6 / Jlog6
-    const double h = dsqrt(z * zc);            // sin(theta)/2
-    const double r = drcp(dmax(theta * h, 1e-300));
-    const double inv_t = r * h, inv_h = r * theta;
+    double h, inv_t, inv_h;                    // sin(theta)/2, 1/theta, 2/sin(theta)
+    if (LEAN) {
+        // The two floors serve theta = 0 (z = 0), where only the Taylor arms of the selects are used and the other arms need no more
+        // than to be FINITE (a discarded inf - inf would still be evaluated): 1/h <= 2^100 and 1/theta <= 2^200 keep the largest
+        // products of the discarded arms, 1/theta^4 = 2^800 and 1/(theta^2 h^2) = 2^600, in range.  Neither floor is reached where
+        // its value is used: the other arms are taken from theta = 2^-13 on, where z zc >= 2^-29 -- and at theta = pi, where
+        // z zc = 2^-104 by the floor of zc above.
+        const double zz = z * zc;
+        inv_h = drsqrt(dmax(zz, 0x1p-200));
+        h = zz * inv_h;
+        inv_t = drcp(dmax(theta, 0x1p-200));
+    } else {
+        h = dsqrt(z * zc);
+        const double r = drcp(dmax(theta * h, 1e-300));
+        inv_t = r * h;
+        inv_h = r * theta;
+    }
     const double cot = zc * inv_h;             // sin / (1 - cos)
     const bool small = theta < kTaylorPrec3;
     const double t2 = theta * theta;
@@ -561,12 +581,15 @@ IKD_FN void log6_and_jlog6_hot(const double (&Re)[9], const double (&pe)[3], Log
     double pp[3];
     rotT_vec(Re, pe, pp);
     pp[0] = -pp[0]; pp[1] = -pp[1]; pp[2] = -pp[2];
+    // LEAN: Jlog3's diagonal term is alpha itself -- the same expression from theta = 2^-13 on, and below it the Taylor form
+    // 1 - t^2/12 to the bit (alpha's own t^4/720 is under half an ulp of 1 there, see above) --, and the symmetric part a3 u u^T is
+    // formed once per pair i <= j.
     const double a3 = beta;
-    const double diag = dsel(small, 0.5 * (2.0 - t2 * (1.0 / 6.0)), 0.5 * (theta * cot));
+    const double diag = LEAN ? alpha : dsel(small, 0.5 * (2.0 - t2 * (1.0 / 6.0)), 0.5 * (theta * cot));
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) o.A[3 * i + j] = a3 * u[i] * u[j];
+        for (int j = 0; j < 3; ++j) o.A[3 * i + j] = (LEAN && j < i) ? o.A[3 * j + i] : a3 * u[i] * u[j];
     o.A[0] += diag; o.A[4] += diag; o.A[8] += diag;
     o.A[1] -= 0.5 * u[2]; o.A[2] += 0.5 * u[1];
     o.A[3] += 0.5 * u[2]; o.A[5] -= 0.5 * u[0];
@@ -630,6 +653,50 @@ IKD_FN void chol_solve(double (&G)[M * M], const double (&b)[M], double (&x)[M])
 #pragma unroll
     for (int k = M - 1; k >= 0; --k) {
         x[k] = y[k] * G[k * M + k];
+#pragma unroll
+        for (int m = 0; m < k; ++m) y[m] = dfma(-G[k * M + m], x[k], y[m]);
+    }
+}
+
+// The same solve by an in-place unpivoted L D L^T: the strict lower triangle is replaced by the unit-diagonal L, the
+// diagonal by 1/D_kk.  This is `JJ.ldlt().solve(et)` (reference ik/ik/dls.cpp:53) without the pivoting: every pivot of
+// JJ = J J^T + lambda^2 I is >= lambda^2 > 0, and the unpivoted factorisation solves the same system within kappa(G) ulp
+// (tests/test_ldlt_solve_host.py).  The solve of the CHAIN programs (device/chain_solver.hpp,
+// device/chain_hot.hpp), every job of a build alike; the tree program keeps chol_solve above: it has fewer FP64
+// instructions with this form too, but at 491 of 512 registers its allocation came out with more copies through the
+// accumulation registers and a longer loop (tools/kernel_stats.py: 5719 -> 5761 issue slots).
+template <int M>
+IKD_FN void ldlt_solve(double (&G)[M * M], const double (&b)[M], double (&x)[M]) {
+    // Right-looking (outer-product) form with the right-hand side carried as an extra row: once the multipliers
+    // l_ik = G_ik / D_kk of column k are known, every trailing update G_ij -= l_ik G_jk (G_jk: the UNSCALED entry)
+    // is an independent FMA, so the reciprocal of the next pivot overlaps them instead of waiting behind a dependent
+    // dot-product chain (the kernels run one wave per SIMD: latency is exposed).  Per pivot: one reciprocal and the
+    // M - 1 - k multipliers -- L L^T also scaled y_k and, in the back substitution, multiplied by the diagonal again.
+    double y[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) y[k] = b[k];
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        const double inv = drcp(G[k * M + k]);
+        G[k * M + k] = inv;
+#pragma unroll
+        for (int i = k + 1; i < M; ++i) {
+            const double l = G[i * M + k] * inv;
+#pragma unroll
+            for (int j = k + 1; j <= i; ++j) G[i * M + j] = dfma(-l, G[j * M + k], G[i * M + j]);
+            y[i] = dfma(-l, y[k], y[i]);
+        }
+        // (the multipliers go over the column only now: row j > k of the update above read G_jk unscaled)
+#pragma unroll
+        for (int i = k + 1; i < M; ++i) G[i * M + k] = G[i * M + k] * inv;
+    }
+    // D^-1 once, then back substitution with the unit-diagonal L^T, column-oriented: once x_k is known every remaining
+    // y_m is updated independently
+#pragma unroll
+    for (int k = 0; k < M; ++k) y[k] = y[k] * G[k * M + k];
+#pragma unroll
+    for (int k = M - 1; k >= 0; --k) {
+        x[k] = y[k];
 #pragma unroll
         for (int m = 0; m < k; ++m) y[m] = dfma(-G[k * M + m], x[k], y[m]);
     }

@@ -44,7 +44,7 @@ extern "C" __global__ void k_chol(const double *in, double *out) {
         for (int j = 0; j <= i; ++j) G[6 * i + j] = in[(6 * i + j) * 64 + threadIdx.x];
 #pragma unroll
     for (int i = 0; i < 6; ++i) e[i] = in[(36 + i) * 64 + threadIdx.x];
-    chol_solve<6>(G, e, y);
+    ldlt_solve<6>(G, e, y);
 #pragma unroll
     for (int i = 0; i < 6; ++i) out[i * 64 + threadIdx.x] = y[i];
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """FP64 instructions of the headline loop by phase (the latency build's costing): tools/hot_phase_count.hip wraps
-each function of device/chain_hot.hpp -- the seven sincos, hot_evaluate (which contains them), hot_gram, chol_solve<6>, hot_step -- for
+each function of device/chain_hot.hpp -- the seven sincos, hot_evaluate (which contains them), hot_gram, ldlt_solve<6>, hot_step -- for
 the Cassie leg's structure code in a kernel of its own; this compiles it to assembly (no GPU) and counts.
     python tools/hot_phase_count.py"""
 import collections
