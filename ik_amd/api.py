@@ -618,6 +618,97 @@ def dls_track_batch(problem, Q0, targets, data, visitor=None, p=None, layout="so
     return Q, ok, it
 
 
+def _check_line_inputs(who, Q0, goals, model, ntasks, lay, data):
+    """Shape, dtype, device and contiguity of (Q0, goals) of the line entries, shapes first (they need no device).  Returns B."""
+    import torch
+    if len(Q0.shape) != 2 or len(goals.shape) != 3:
+        raise ValueError("Q0 has shape %s and goals %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(goals.shape)))
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(goals.shape), model.nq, ntasks, B, lay)
+    if not (isinstance(Q0, torch.Tensor) and isinstance(goals, torch.Tensor) and Q0.is_cuda and goals.is_cuda
+            and Q0.dtype == torch.float64 and goals.dtype == torch.float64):
+        raise TypeError("%s needs float64 CUDA tensors" % who)
+    if not (Q0.is_contiguous() and goals.is_contiguous()):
+        raise ValueError("%s needs contiguous tensors" % who)
+    if Q0.device.index != data._device or goals.device.index != data._device:
+        raise ValueError("tensors live on cuda:%s / cuda:%s but the problem was created on device %d"
+                         % (Q0.device.index, goals.device.index, data._device))
+    return B
+
+
+def _check_waypoints(T):
+    if not isinstance(T, int) or T < 0:
+        raise ValueError("T must be a non-negative integer, got %r" % (T,))
+
+
+def line_targets(problem, Q0, goals, data, T, layout="soa"):
+    """The T waypoints of the straight Cartesian line from the pose of every task frame at Q0 to its goal (include/ikgpu.h
+    ikgpu_line_targets): waypoint k has s = (k + 1) / T, R = R0 exp3(s log3(R0^T R1)), p = p0 + s (p1 - p0); waypoint T - 1 is the goal
+    itself.  Every target slot must be a FrameTask's, with a reference frame fixed in the world.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], goals [ntasks, 12, B]   |   "aos": Q0 [B, nq], goals [B, ntasks, 12].
+    Returns W [T, ntasks, 12, B] | [T, B, ntasks, 12], the shape of dls_track_batch's targets."""
+    import torch
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    _check_waypoints(T)
+    B = _check_line_inputs("line_targets", Q0, goals, model, ntasks, lay, data)
+    W = torch.empty((T,) + tuple(goals.shape), dtype=torch.float64, device=Q0.device)
+    data._bind(problem)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream
+    capi.check(capi.lib().ikgpu_line_targets(data._h, B, T, Q0.data_ptr(), goals.data_ptr(), W.data_ptr(), lay, C.c_void_p(s)))
+    return W
+
+
+def dls_line_kernel(data, visitor=None, p=None):
+    """Name of what dls_line_batch runs for these parameters: "dls_chain_line<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_line_kernel(data._h, C.byref(prm)).decode()
+
+
+def dls_line_batch(problem, Q0, goals, data, T, visitor=None, p=None, layout="soa", out=None, stream=None):
+    """Can the task frame travel in a straight line from where it is at Q0 to its goal, and along which joint trajectory?
+    dls_track_batch on line_targets(problem, Q0, goals, data, T), a problem taking part in waypoint k only while all its earlier
+    waypoints met the stop rule.  reached[b] counts the waypoints met before the first failure (T: the goal was reached); slabs
+    k <= min(reached[b], T - 1) of problem b are written and bit-identical to dls_track_batch on those waypoints, later slabs are
+    unspecified.  A chain problem runs one launch that reads the goal alone and leaves a failed line at once.  A relative rotation near
+    pi has an ill-conditioned axis: split such a move.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], goals [ntasks, 12, B]   |   "aos": Q0 [B, nq], goals [B, ntasks, 12].
+    out: (Q [T, nq, B] | [T, B, nq], success uint8 [T, B], iterations int32 [T, B], reached int32 [B]) preallocated, or None.
+    Returns (Q, success, iterations, reached)."""
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    _check_waypoints(T)
+    B = _check_line_inputs("dls_line_batch", Q0, goals, model, ntasks, lay, data)
+    q_shape = (T, model.nq, B) if lay == capi.SOA else (T, B, model.nq)
+    if out is None:
+        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
+        ok = torch.empty((T, B), dtype=torch.uint8, device=Q0.device)
+        it = torch.empty((T, B), dtype=torch.int32, device=Q0.device)
+        reached = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+    else:
+        Q, ok, it, reached = out
+        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
+        _check_tensor("out[1] (success)", ok, (T, B), torch.uint8, data._device)
+        _check_tensor("out[2] (iterations)", it, (T, B), torch.int32, data._device)
+        _check_tensor("out[3] (reached)", reached, (B,), torch.int32, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_line_workspace_bytes(data._h, B, T, C.byref(prm))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_line_batch(data._h, B, T, Q0.data_ptr(), goals.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
+                                      reached.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    return Q, ok, it, reached
+
+
 def dls_multistart_kernel(data, visitor=None, p=None, num_starts=8):
     """Name of what dls_multistart_batch runs for these parameters: "dls_chain_multistart<...>" (one launch) or "loop(<data.kernel>)"."""
     prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())

@@ -926,6 +926,129 @@ int ikgpu_dls_track_batch(const ikgpu_problem *p, int64_t B, int64_t T, const do
     });
 }
 
+}  // extern "C"
+
+namespace {
+
+// ikgpu_line_targets takes a problem whose every target slot is a FrameTask's pose in a reference frame fixed in the world.
+int check_line_slots(const ikgpu_problem *p) {
+    const ikgpu::ProblemHost &g = p->gen;   // (the generic analysis: every kind has one, slot i is task i)
+    for (int i = 0; i < g.ntasks; ++i) {
+        const int type = g.tasks[static_cast<size_t>(i)].type;
+        if (type != IKGPU_POSITION && type != IKGPU_ORIENTATION && type != IKGPU_FULL)
+            return fail(IKGPU_ERR_UNSUPPORTED, "target slot " + std::to_string(i) + " is not a FrameTask's pose (alignment, posture and "
+                                                   "centre-of-mass slots have no line)");
+        if (g.generic.ints[static_cast<size_t>(g.generic.o_trjoint + i)] != 0)
+            return fail(IKGPU_ERR_UNSUPPORTED, "target slot " + std::to_string(i) + ": the reference frame moves with the configuration");
+    }
+    return IKGPU_OK;
+}
+
+// ikgpu_line_targets for validated arguments, inside on_device.
+int dispatch_line_targets(const ikgpu_problem *p, int64_t B, int T, const double *q0, const double *goals, double *W, int layout, hipStream_t st) {
+    if (p->host.kind == ikgpu::KernelKind::Chain)
+        return launched(ikgpu::launch_line_targets_chain(p->host, p->dev, B, T, q0, goals, W, layout, st), "launching the line waypoint kernel");
+    // every other kind: oMf(q0) of every slot into slab 0 (what ikgpu_task_frames_fk_batch launches), then the waypoints over it
+    const hipError_t e = p->host.kind == ikgpu::KernelKind::Tree && !p->host.tree_extras()
+                             ? ikgpu::launch_eval_tree(p->host, p->dev, B, q0, q0, nullptr, nullptr, W, layout, st)
+                             : ikgpu::launch_eval_generic(p->gen, p->dev, B, q0, q0, nullptr, nullptr, W, layout, st);
+    if (e != hipSuccess) return hip_fail(e, "launching the FK kernel");
+    return launched(ikgpu::launch_line_targets_from_fk(B, p->gen.ntasks, T, p->dev.g_dbls + p->gen.generic.o_trpl, goals, W, layout, st),
+                    "launching the line waypoint kernel");
+}
+
+// The workspace of the line definition run as a loop, carved as start_workspace: the waypoints [T][ntasks x 12 x B], then the success
+// flags [T][B] (used when the caller passed none).
+struct LineWorkspace {
+    size_t targets, success, total;
+};
+LineWorkspace line_workspace(const ikgpu_problem *p, int64_t B, int64_t T) {
+    size_t end = 0;
+    auto take = [&](size_t n) { const size_t at = end; end += (n + 255) / 256 * 256; return at; };
+    const size_t b = static_cast<size_t>(B), t = static_cast<size_t>(T);
+    LineWorkspace w{};
+    w.targets = take(8 * 12 * static_cast<size_t>(p->gen.ntasks) * b * t);
+    w.success = take(b * t);
+    w.total = end;
+    return w;
+}
+
+int check_line_call(const ikgpu_problem *p, int64_t B, int64_t T, int layout) {
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = refuse_if(T < 0, "negative number of waypoints")) return rc;
+    return check_layout(layout);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ikgpu_line_targets(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *goals, double *W_out, int layout,
+                       void *stream) {
+    if (int rc = check_line_call(p, B, T, layout)) return rc;
+    if (B == 0 || T == 0) return IKGPU_OK;  // nothing to write (the pointers may be null; the problem is not looked at)
+    if (!q0 || !goals || !W_out) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
+    if (int rc = refuse_if(T > 0x7fffffff, "too many waypoints for one call")) return rc;
+    if (int rc = check_line_slots(p)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) { return dispatch_line_targets(p, B, static_cast<int>(T), q0, goals, W_out, layout, st); });
+}
+
+const char *ikgpu_dls_line_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    name = variant_kernel_name(p, track_is_fused(p, params), "_line");
+    return name.c_str();
+}
+
+size_t ikgpu_dls_line_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t T, const ikgpu_dls_params *params) {
+    if (!p || !params || B <= 0 || T <= 0 || track_is_fused(p, params)) return 0;
+    return line_workspace(p, B, T).total;
+}
+
+int ikgpu_dls_line_batch(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *goals, const ikgpu_dls_params *params,
+                         double *q_traj, uint8_t *success, int32_t *iters, int32_t *reached, int layout, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+    if (int rc = check_line_call(p, B, T, layout)) return rc;
+    if (int rc = check_params(params)) return rc;
+    if (params->stop_sq_tol < 0.0 && !ikgpu::visitor_extended(*params))
+        return fail(IKGPU_ERR_INVALID, "the never-stop visitor reaches no waypoint: a line needs a stop rule (stop_sq_tol >= 0)");
+    if (B == 0 || T == 0) return IKGPU_OK;  // nothing to solve (the pointers may be null; the problem is not looked at)
+    if (!q0 || !goals || !q_traj) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
+    if (int rc = refuse_if(T > 0x7fffffff, "too many waypoints for one call")) return rc;
+    if (int rc = check_line_slots(p)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        if (track_is_fused(p, params)) {
+            const ikgpu::BatchIO io{B, q0, goals, q_traj, success, iters, layout};
+            ikgpu::ChainJob job{};
+            job.kind = ikgpu::ChainJob::Line;
+            job.line = ikdev::LineArgs{reached, static_cast<int>(T)};
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the DLS line kernel");
+        }
+        // every other kind: the definition itself -- the waypoints, the chained calls, the count of leading successes
+        const LineWorkspace w = line_workspace(p, B, T);
+        if (!workspace || workspace_bytes < w.total)
+            return fail(IKGPU_ERR_INVALID, "line workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                               std::to_string(w.total) + " needed (ikgpu_dls_line_workspace_bytes)");
+        char *ws = static_cast<char *>(workspace);
+        double *W = reinterpret_cast<double *>(ws + w.targets);
+        uint8_t *ok = success ? success : reinterpret_cast<uint8_t *>(ws + w.success);
+        if (const int rc = dispatch_line_targets(p, B, static_cast<int>(T), q0, goals, W, layout, st)) return rc;
+        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B, t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
+        for (int64_t k = 0; k < T; ++k) {
+            const ikgpu::BatchIO io{B, k == 0 ? q0 : q_traj + (k - 1) * q_slab, W + k * t_slab, q_traj + k * q_slab, ok + k * B,
+                                    iters ? iters + k * B : nullptr, layout};
+            if (const int rc = dispatch_dls(p, io, params, st)) {
+                g_last_error = "waypoint " + std::to_string(k) + ": " + g_last_error;
+                return rc;
+            }
+        }
+        if (!reached) return static_cast<int>(IKGPU_OK);
+        return launched(ikgpu::launch_line_reached(B, static_cast<int>(T), ok, reached, st), "launching the line count");
+    });
+}
+
 const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
     if (!p || !params) return "";
     thread_local std::string name;

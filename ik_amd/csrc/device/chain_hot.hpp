@@ -367,12 +367,11 @@ IKD_FN void hot_step(const Tab &t, const LoopParams &prm, const double (&col)[NJ
 }
 
 // One full solve.  q: in = q0 (chain joints), out = result.  NEVERSTOP: the visitor never stops (stop_sq_tol < 0): every
-// lane takes exactly max_iterations steps.
+// lane takes exactly max_iterations steps.  active: false for a lane that takes no part in this solve (chain_solver.hpp chain_dls).
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
 IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const double (&oMt)[12], int &iters_out,
-                    bool &success_out, AnyFn any_active) {
+                    bool &success_out, AnyFn any_active, bool active = true) {
     constexpr int M = 6;
-    bool active = true;
     bool success = false;
     int iters = prm.max_iterations;
 #pragma unroll 1
@@ -557,6 +556,46 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
     }
 }
 
+// A straight Cartesian line to one goal per problem -- dls_chain_line_body (chain_kernel_body.hpp: the definition, the lane's order of
+// work, which slabs are written) with the hot program.  The start pose comes from the chain table in HBM (a.desc, the stage kernels'
+// FK), not from the compact table: once per launch, and the bits of ikgpu_line_targets.  Between waypoints the lane parks q, the start
+// pose, the rotation vector and the goal (27 doubles); nothing is loaded per waypoint, so no wait stands between two solves.
+template <int NJ, class S, class Tab, class AnyFn>
+IKD_FN int hot_line_body(const ChainKernelArgs<NJ> &a, const Tab &t, const LineArgs &la, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
+    const bool valid = gid < a.B;
+    const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B;
+    double q[NJ], goal[12];
+    line_load(a, b, q, goal);
+    LineStart ls;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
+    line_chain_start(a, *(ConstDesc *)a.desc, q, goal, ls);
+    bool alive = true, stepped = false;
+    int reached = 0, k = 0;
+    for (; k < la.T && IKD_ANY(alive); ++k) {
+        double w[12], oMt[12];
+        line_waypoint(ls, goal, k, la.T, w);
+        compose_target(a, w, oMt);
+        int iters;
+        bool success;
+        hot_dls<NJ, S, false>(t, a.prm, q, oMt, iters, success, any_active, alive);   // (any_active by value: a fresh count per waypoint)
+        stepped = stepped || (alive && iters > 0);
+        if (valid && alive) {
+            double *q_out = a.q_out + k * q_slab;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
+            if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
+            if (a.iters) a.iters[k * a.B + b] = iters;
+            hot_pass_through_to(a, q_out, b, stepped);
+        }
+        alive = alive && success;
+        reached += alive ? 1 : 0;
+    }
+    if (valid && la.reached) la.reached[b] = reached;
+    return k;
+}
+
 // K starts per problem, the best one stored -- dls_chain_multistart_body (chain_kernel_body.hpp: the definition, the lane mapping, the
 // three pieces) with the hot program: the unchanged hot_dls, then one more hot_evaluate at its result for the error alone (its Jacobian
 // columns are dead code).
@@ -659,6 +698,14 @@ __device__ __forceinline__ void hot_track_entry(const ChainKernelArgs<NJ> &a, co
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
     hot_track_body<NJ, S, NEVERSTOP>(a, tv, T, gid, KeepGoing{0, 0, 0});
+}
+
+template <int NJ, class S>
+__device__ __forceinline__ void hot_line_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const LineArgs &la) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
+    HotTable tv;
+    hot_park_table<NJ, S>(t, tv);
+    (void)hot_line_body<NJ, S>(a, tv, la, gid, KeepGoing{0, 0, 0});
 }
 
 template <int NJ, class S, bool NEVERSTOP>

@@ -7,6 +7,7 @@
 #endif
 
 #include "chain_solver.hpp"
+#include "line.hpp"
 #include "multistart.hpp"
 #include "solutions.hpp"
 
@@ -210,6 +211,71 @@ IKD_FN void dls_chain_track_body(const ChainKernelArgs<NJ> &a, const Desc &d, in
         }
         if (k + 2 < T) load_target_raw(a, a.targets + (k + 2) * t_slab, b, next);
     }
+}
+
+// ---- line: follow a straight Cartesian line from the pose at q0 to ONE goal per problem (include/ikgpu.h ikgpu_dls_line_batch) ----------
+// Defined as the tracking call above on the T waypoints of ikgpu_line_targets, a problem taking part in waypoint k only while all its
+// earlier waypoints met the stop rule.  The lane loads q0 and its goal (twelve doubles, not T x 12), runs the stage kernels' FK at q0
+// and forms the start pose and the rotation vector once (device/line.hpp: the source of ikgpu_line_targets too, hence the same bits);
+// per waypoint it forms the raw target, hands it to compose_target where the tracking body hands a loaded one, and solves with q
+// on-chip.  A lane whose line has failed enters the later waypoints inactive (chain_dls: its q stays, it keeps no other lane waiting)
+// and stores nothing more; the wave leaves the waypoint loop once none of its lanes is alive.  Slabs 0 .. min(reached, T - 1) of a
+// problem are written -- the failed waypoint's among them, success = 0 -- and hold the tracking call's bits; entries of q outside the
+// chain as there.  Needs a stop rule (without one nothing is ever reached: the entry point refuses the call).
+// Returns the waypoints this lane's wave went through (the host-side lane emulator reads it; a kernel ignores it).
+template <int NJ>
+IKD_FN void line_load(const ChainKernelArgs<NJ> &a, int64_t b, double (&q)[NJ], double (&goal)[12]) {
+    const ChainStrides st = chain_strides(a);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
+    load_target_raw(a, a.targets, b, goal);
+}
+// The start of the line of a chain problem: FK at q from the chain table in HBM (a.desc), through scalar loads on the device.
+template <int NJ, class Desc>
+IKD_FN void line_chain_start(const ChainKernelArgs<NJ> &a, const Desc &d, const double (&q)[NJ], const double (&goal)[12], LineStart &ls) {
+    double Rf[9], pf[3];
+    line_chain_fk<NJ>(d, a.prm.idmask, q, Rf, pf);
+    line_start(a.ref_pl, Rf, pf, goal, ls);
+}
+
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN int dls_chain_line_body(const ChainKernelArgs<NJ> &a, const Desc &d, const LineArgs &la, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
+    const bool valid = gid < a.B;
+    const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B;
+    double q[NJ], goal[12];
+    line_load(a, b, q, goal);
+    LineStart ls;
+    line_chain_start(a, d, q, goal, ls);
+    bool alive = true, stepped = false;
+    int reached = 0, k = 0;
+    for (; k < la.T && IKD_ANY(alive); ++k) {
+        double t[12], oMt[12];
+        line_waypoint(ls, goal, k, la.T, t);
+        compose_target(a, t, oMt);
+        int iters;
+        bool success;
+        chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active, alive);   // (any_active by value: a fresh count per waypoint)
+        stepped = stepped || (alive && iters > 0);
+        if (valid && alive) {
+            double *q_out = a.q_out + k * q_slab;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
+            if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
+            if (a.iters) a.iters[k * a.B + b] = iters;
+            for (int i = 0; i < a.nq; ++i) {
+                if (a.q_in_chain[i]) continue;
+                const double v = a.q0[at(st.elem, st.q_prob, i, b)];
+                const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
+                q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
+            }
+        }
+        alive = alive && success;
+        reached += alive ? 1 : 0;
+    }
+    if (valid && la.reached) la.reached[b] = reached;
+    return k;
 }
 
 // ---- multi-start: K starts per problem in one launch, the best one stored (include/ikgpu.h ikgpu_dls_multistart_batch) ----------------

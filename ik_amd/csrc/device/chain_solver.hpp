@@ -257,10 +257,11 @@ IKD_FN int iterations_taken(const KeepGoing &k, int) { return k.n; }
 
 // One full solve. q: in = q0 (chain joints only), out = result. Returns iterations / success.
 // any_active(bool) must return a wave-uniform "some lane still iterating" (identity on the host).
+// active: false for a lane that takes no part in this solve (a line job's lane whose line has failed, chain_kernel_body.hpp
+// dls_chain_line_body): its q stays, its iters_out / success_out mean nothing.
 template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
 IKD_FN void chain_dls(const Desc &d_in, const LoopParams &prm, double (&q)[NJ], const double (&oMt)[12],
-                      int &iters_out, bool &success_out, AnyFn any_active) {
-    bool active = true;
+                      int &iters_out, bool &success_out, AnyFn any_active, bool active = true) {
     bool success = false;
     int iters = prm.max_iterations;
     const Desc *dp = &d_in;

@@ -703,6 +703,31 @@ inline void dls_track_device(InverseKinematicsProblem &problem, std::int64_t B, 
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// A straight Cartesian line from the pose of every task frame at Q0 to one goal per problem on DEVICE buffers: dls_track_device on the
+// T waypoints ikgpu_line_targets defines (the caller's target sequence as a formula, ik_ros/src/cassie.cpp:92-113), a problem taking
+// part in waypoint k only while its earlier waypoints met the stop rule (ik/ik/dls.cpp:61-64,76-77).  goals [ntasks][12][B];
+// Q [T][nq][B], success / iterations [T][B] (may be null): slabs k <= min(reached[b], T - 1) are written; reached [B] (may be null)
+// counts the waypoints met before the first failure.  workspace: device memory of line_workspace_bytes() bytes (0 for a chain problem:
+// one launch).  Asynchronous on `stream`.
+inline std::size_t line_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, std::int64_t T, dls_data &data,
+                                        const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                        const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_line_workspace_bytes(data.handle(), B, T, &prm);
+}
+inline void dls_line_device(InverseKinematicsProblem &problem, std::int64_t B, std::int64_t T, const number_t *Q0, const number_t *goals,
+                            dls_data &data, number_t *Q, std::uint8_t *success, std::int32_t *iterations, std::int32_t *reached,
+                            void *workspace, std::size_t workspace_bytes, void *stream,
+                            const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                            const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_line_batch(data.handle(), B, T, Q0, goals, &prm, Q, success, iterations, reached, IKGPU_SOA, workspace, workspace_bytes,
+                             stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // The best of K starts per problem on DEVICE buffers (ik::dls is a local method: ik/ik/dls.cpp:10 "try random walk", dls.cpp:73
 // "perform random restart"; dls_parameters::random_restart, ik/ik/dls.hpp:27, stays inert and ik::dls() is unchanged).  Start 0 is Q0,
 // starts 1 .. K-1 are `starts` [K-1][nq][B] or, when null, generated from `seed`; the winner is the lowest-index start that met the stop

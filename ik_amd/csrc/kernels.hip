@@ -77,6 +77,73 @@ __global__ __launch_bounds__(kBlock) void dls_chain_track_kernel(const ChainKern
     ikdev::dls_chain_track_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, T, gid, ikdev::KeepGoing{0, 0, 0});
 }
 
+// A straight Cartesian line to one goal per problem in one launch (device/chain_kernel_body.hpp dls_chain_line_body): the general build's
+// line kernel.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_line_kernel(const ChainKernelArgs<NJ> a, const ikdev::LineArgs la) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    (void)ikdev::dls_chain_line_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, la, gid, ikdev::KeepGoing{0, 0, 0});
+}
+
+// The waypoints of ikgpu_line_targets for a chain problem: a.targets holds the goals, a.oMf_out the T slabs.
+template <int NJ>
+__global__ __launch_bounds__(kBlock) void line_targets_chain_kernel(const ChainKernelArgs<NJ> a, const int T) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (b >= a.B) return;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;
+    double q[NJ], goal[12];
+    ikdev::line_load(a, b, q, goal);
+    ikdev::LineStart ls;
+    ikdev::line_chain_start(a, *(ConstDesc *)a.desc, q, goal, ls);
+    for (int k = 0; k < T; ++k) {
+        double t[12];
+        ikdev::line_waypoint(ls, goal, k, T, t);
+        double *out = a.oMf_out + static_cast<int64_t>(k) * 12 * a.B;
+#pragma unroll
+        for (int c = 0; c < 12; ++c) out[ikdev::at(a.layout, a.B, 12, c, b)] = t[c];
+    }
+}
+
+struct LineTargetsArgs {
+    const double *ref_pl, *goals;
+    double *out;
+    int64_t B;
+    int ntasks, T, layout;
+};
+__global__ __launch_bounds__(256) void line_targets_from_fk_kernel(const LineTargetsArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= a.B * a.ntasks) return;
+    const int64_t b = i % a.B;
+    const int s = static_cast<int>(i / a.B);
+    double f[12], goal[12], ref[12];
+#pragma unroll
+    for (int c = 0; c < 12; ++c) {
+        const int64_t at = ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b);
+        f[c] = a.out[at];   // slab 0: oMf(q0) of this slot, read before waypoint 0 goes over it
+        goal[c] = a.goals[at];
+        ref[c] = a.ref_pl[s * 12 + c];
+    }
+    const double Rf[9] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]}, pf[3] = {f[9], f[10], f[11]};
+    ikdev::LineStart ls;
+    ikdev::line_start(ref, Rf, pf, goal, ls);
+    for (int k = 0; k < a.T; ++k) {
+        double t[12];
+        ikdev::line_waypoint(ls, goal, k, a.T, t);
+        double *out = a.out + static_cast<int64_t>(k) * a.ntasks * 12 * a.B;
+#pragma unroll
+        for (int c = 0; c < 12; ++c) out[ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b)] = t[c];
+    }
+}
+
+__global__ __launch_bounds__(256) void line_reached_kernel(int64_t B, int T, const uint8_t *success, int32_t *reached) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= B) return;
+    int n = 0;
+    while (n < T && success[n * B + b]) ++n;
+    reached[b] = n;
+}
+
 // K starts per problem in one launch, the best one stored (device/chain_kernel_body.hpp dls_chain_multistart_body): the general build's
 // multi-start kernel.
 template <int NJ, int KT, int SMASK>
@@ -241,8 +308,9 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         constexpr int SM = decltype(smask)::value;
         if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
         const dim3 grid = grid_for(job.lanes(io.B));
-        if (job.kind == ChainJob::Solutions && prm.stop_sq_tol < 0.0) return hipErrorInvalidValue;
-        if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
+        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line) && prm.stop_sq_tol < 0.0) return hipErrorInvalidValue;
+        if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
+        else if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
         else if (job.kind == ChainJob::Solutions) hipLaunchKernelGGL((dls_chain_solutions_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.sol);
         else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.ms);
         return hipGetLastError();
@@ -412,6 +480,34 @@ hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const
     IKGPU_FOR_NJ(X)
 #undef X
     not_built(nj, type);
+}
+
+hipError_t launch_line_targets_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, int T, const double *q0, const double *goals,
+                                     double *out, int layout, hipStream_t stream) {
+    const int nj = ph.chain.nj;
+#define X(N)                                                                                                 \
+    if (nj == N) {                                                                                           \
+        ChainKernelArgs<N> a = make_args<N>(ph, dt);                                                         \
+        a.layout = layout; a.B = B; a.q0 = q0; a.targets = goals; a.oMf_out = out;                           \
+        hipLaunchKernelGGL((line_targets_chain_kernel<N>), grid_for(B), dim3(kBlock), 0, stream, a, T);      \
+        return hipGetLastError();                                                                            \
+    }
+    IKGPU_FOR_NJ(X)
+#undef X
+    not_built(nj, 0);
+}
+
+hipError_t launch_line_targets_from_fk(int64_t B, int ntasks, int T, const double *ref_pl, const double *goals, double *out, int layout,
+                                       hipStream_t stream) {
+    const LineTargetsArgs a{ref_pl, goals, out, B, ntasks, T, layout};
+    const int64_t n = B * ntasks;
+    hipLaunchKernelGGL(line_targets_from_fk_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_line_reached(int64_t B, int T, const uint8_t *success, int32_t *reached, hipStream_t stream) {
+    hipLaunchKernelGGL(line_reached_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, T, success, reached);
+    return hipGetLastError();
 }
 
 hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,

@@ -8,6 +8,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device/line.hpp"
 #include "device/multistart.hpp"
 #include "device/solutions.hpp"
 #include "problem.hpp"
@@ -77,12 +78,18 @@ struct BatchIO {
 //   Solutions:  the same B x K lanes, the distinct converged starts stored, up to sol.N per problem (ikgpu_dls_solutions_batch;
 //               dls_chain_solutions_body, hot_solutions_body): `io.q_out` / `io.iters` are [N] slabs, `io.success` is not written.  Needs a
 //               stop rule (the never-stop visitor converges nowhere): a launcher refuses the job without one.
-// Track, Multistart and Solutions are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is capturable.
+//   Line:       T chained solves per problem in ONE launch along the straight line from the pose at q0 to the problem's goal
+//               (ikgpu_dls_line_batch; dls_chain_line_body, hot_line_body): `io.targets` holds ONE goal per problem, the waypoints are
+//               formed on the lane (device/line.hpp), a problem stops at its first failed waypoint and line.reached counts the ones
+//               before it.  Needs a stop rule, as Solutions.
+// Track, Multistart, Solutions and Line are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
+// capturable.
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart, Solutions } kind = Solve;
+    enum Kind { Solve, Track, Multistart, Solutions, Line } kind = Solve;
     int T = 0;                     // Track: the number of waypoints
     ikdev::MultistartArgs ms{};    // Multistart
     ikdev::SolutionsArgs sol{};    // Solutions
+    ikdev::LineArgs line{};        // Line
     int64_t lanes(int64_t B) const {   // one lane per problem, or per start
         return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : B;
     }
@@ -95,6 +102,16 @@ hipError_t launch_eval_chain(const ProblemHost &ph, const DeviceTables &dt, int6
                              double *e_out, double *J_out, int layout, hipStream_t stream);
 hipError_t launch_fk_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, const double *q, double *oMf_out, int layout,
                            hipStream_t stream);
+// The T waypoints of ikgpu_line_targets (device/line.hpp) into `out` [T][ntasks x 12 x B].  A chain problem: FK at q0 and the waypoints in
+// one kernel, on the arithmetic the fused line kernels use.
+hipError_t launch_line_targets_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, int T, const double *q0, const double *goals,
+                                     double *out, int layout, hipStream_t stream);
+// Every other kind: `out`'s slab 0 holds oMf(q0) of every target slot (what ikgpu_task_frames_fk_batch launches wrote there); ref_pl
+// [ntasks x 12] (device) are the world placements of the slots' reference frames.  Each thread reads its own slot before it writes.
+hipError_t launch_line_targets_from_fk(int64_t B, int ntasks, int T, const double *ref_pl, const double *goals, double *out, int layout,
+                                       hipStream_t stream);
+// reached[b] = the number of leading ones in success[0 .. T-1][b] (ikgpu_dls_line_batch run as the loop over the single solve).
+hipError_t launch_line_reached(int64_t B, int T, const uint8_t *success, int32_t *reached, hipStream_t stream);
 // Starts k0 .. k1-1 (1 <= k0 <= k1) of every problem as ikgpu_multistart_starts defines them, start k into slab k - k0 of `out`.
 hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,
                                     int layout, hipStream_t stream);

@@ -62,6 +62,13 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_solutions_kernel(const C
     ikdev::hot_solutions_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, sa);
 }
 
+// A straight Cartesian line to one goal per problem in one launch (device/chain_hot.hpp hot_line_body; include/ikgpu.h
+// ikgpu_dls_line_batch).  Stop rule only; lock-step per waypoint; no LDS, no queue slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_line_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::LineArgs la) {
+    ikdev::hot_line_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, la);
+}
+
 // X(NJ, code0, code1, code2)
 #define IKGPU_HOT_SHAPES(X)                                                                                                   \
     X(7, 0x04f0208cce8c7664ull, 0x395959cacad65656ull, 0x000001cacace5656ull) /* Cassie leg: Left / RightFootFront, 22 values */ \
@@ -120,6 +127,9 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
         } else if (job.kind == ChainJob::Solutions) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (no start converges without a stop rule: the entry point refuses the call)
             else hipLaunchKernelGGL((dls_chain_hot_solutions_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.sol);
+        } else if (job.kind == ChainJob::Line) {
+            if constexpr (NEVER) return hipErrorInvalidValue;   // (nothing is ever reached without a stop rule: refused likewise)
+            else hipLaunchKernelGGL((dls_chain_hot_line_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.line);
         } else if constexpr (NEVER) {
             hipLaunchKernelGGL((dls_chain_hot_kernel<NJ, C0, C1, C2, true>), grid, block, 0, stream, a, t);
         } else {

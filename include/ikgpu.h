@@ -317,6 +317,49 @@ size_t ikgpu_dls_solutions_workspace_bytes(const ikgpu_problem *p, int64_t B, in
  * ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- and has no such choice.) */
 const char *ikgpu_dls_solutions_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K);
 
+/* ---- line: follow a STRAIGHT Cartesian line from where the task frame is at q0 to one goal per problem -- the approach or retreat of a
+ * grasp, the swing of a foot, a linear move.  The reference's own caller generates its target sequence from a formula on every tick
+ * (ik_ros/src/cassie.cpp:92-113); here the formula is the line, and the T waypoints are a function of q0 and the goal.
+ * ikgpu_line_targets writes them, W_out [T][ntasks x 12 x B] (the shape of ikgpu_dls_track_batch's targets), from
+ *   goals [ntasks x 12 x B]  the shape and meaning of ikgpu_dls_solve_batch's targets: slot by slot the pose M1 = (R1, p1) of the task
+ *                            frame in the task's reference frame;
+ *   M0 = (R0, p0) = oMr^-1 oMf(q0), the pose of the task frame at q0 in that reference frame, w = log3(R0^T R1);
+ *   waypoint k (k = 0 .. T-1), s = (k + 1) / T:   R = R0 exp3(s w),  p = p0 + s (p1 - p0)   for k < T-1
+ *   (a straight line of the frame origin at constant angular velocity), and waypoint T-1 is the goal's own 12 doubles, bit for bit --
+ *   so T == 1 is the single solve to the goal.
+ * log3 follows the rotation part of the error's log6 (theta = acos of the clamped trace, the theta -> pi formula from pi - 1e-2 on);
+ * exp3 is Rodrigues' formula with Taylor forms below theta = 2^-13.  A relative rotation near pi has an ill-conditioned axis: split
+ * such a move into two lines.  Accepted when every target slot belongs to a FrameTask (IKGPU_POSITION / _ORIENTATION / _FULL) whose
+ * reference frame is fixed in the world; alignment, posture and centre-of-mass slots and a reference frame that moves with q are
+ * IKGPU_ERR_UNSUPPORTED.  W_out must not overlap q0 or goals.  DEVICE pointers; asynchronous on `stream`; B == 0 or T == 0 is a
+ * no-op; T < 0 is IKGPU_ERR_INVALID. */
+int ikgpu_line_targets(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *goals,
+                       double *W_out /* [T][ntasks x 12 x B] */, int layout /* ikgpu_layout */, void *stream);
+/* ikgpu_dls_line_batch is DEFINED as ikgpu_dls_track_batch on W = ikgpu_line_targets(q0, goals), with problem b taking part in waypoint
+ * k only while all its earlier waypoints met the stop rule (a problem that has left its line is not solved any further; "met" and "failed" are
+ * the reference's own stop test and failure report, ik/ik/dls.cpp:61-64,76-77; the sequence is the caller's, ik_ros/src/cassie.cpp:92-113):
+ *   reached [B] (int32, may be NULL)  the waypoints met before the first failure; T when the goal was reached
+ *   q_traj [T][nq x B], success [T][B] (may be NULL), iters [T][B] (may be NULL): slabs k <= min(reached[b], T-1) of problem b are
+ *   written -- the failed waypoint's among them, with success = 0 -- and are bit-identical to ikgpu_dls_track_batch on W; later slabs
+ *   of that problem are unspecified.
+ * The argument rules are ikgpu_dls_track_batch's; under the never-stop visitor (stop_sq_tol < 0 and no derived visitor) nothing is
+ * ever reached: IKGPU_ERR_INVALID.  A chain problem under the reference's visitor runs ONE launch (`dls_chain_line<...>`): a lane
+ * loads q0 and its goal (12 doubles, not T x 12), forms the waypoints itself and keeps q in registers; a lane whose line has failed
+ * is inactive from then on and the wave leaves once none of its lanes is alive, so slabs beyond the failed waypoint are NOT written
+ * (no queue slot, no allocation: capturable in a graph; `workspace` is not read).  Every other problem kind and the derived visitors
+ * run the definition from inside the call -- ikgpu_line_targets into `workspace` (DEVICE memory of at least
+ * ikgpu_dls_line_workspace_bytes bytes, else IKGPU_ERR_INVALID), the T launches, and a count of the leading successes (the flags live
+ * in the workspace when success is NULL). */
+int ikgpu_dls_line_batch(const ikgpu_problem *p, int64_t B, int64_t T, const double *q0, const double *goals,
+                         const ikgpu_dls_params *params, double *q_traj, uint8_t *success, int32_t *iters, int32_t *reached,
+                         int layout /* ikgpu_layout */, void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of `workspace` ikgpu_dls_line_batch needs for these arguments: 0 for the single launch. */
+size_t ikgpu_dls_line_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t T, const ikgpu_dls_params *params);
+/* Name of what ikgpu_dls_line_batch runs with these parameters: `dls_chain_line<NJ=7,full,hot>` (or hot-rtc / general: the build
+ * ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the definition run waypoint after
+ * waypoint.  The string belongs to the calling thread and lasts until its next call. */
+const char *ikgpu_dls_line_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
+
 /* FrameTask::target (an SE(3), reference ik/ik/frame.hpp:189) given as 7 doubles -- translation (x y z), quaternion (qx qy qz qw;
  * converted as Eigen's toRotationMatrix does, i.e. as the free-flyer's configuration is read) -- expanded into the 12-double slots
  * the solve entry points take.  pose7: [ntasks x 7 x B] (IKGPU_SOA) or [B x ntasks x 7] (IKGPU_AOS); targets12 likewise with 12.
