@@ -21,6 +21,8 @@ Ten problems are rewritten so that a chain joint starts ON a limit with the firs
 model with the limits lifted) crosses it.  A one-joint chain may yield fewer than ten; Position on l1 yields none -- the frame origin
 lies on the joint axis, the Jacobian is identically zero and no step exists (such a lane stops at iteration 0).
 
+The line job (line_goals): the case's own target, and for every third problem a far goal, T = 8 waypoints under the default stop rule.
+
 SEED was chosen on the CPU, once: the double oracle, the _Float128 oracle (O.dls_batch(..., ext="q")) and the lane emulator agree on
 every success flag and iteration count of every case for 1, 2, 3 fixed iterations and for the default stop rule with 100
 (tests/test_chain_shapes_emulation.py asserts it again on every run)."""
@@ -223,6 +225,54 @@ def waypoints(c):
     way = np.stack([relative_targets(O, x.om_free, x.q0 + f * (x.qs - x.q0), x.fid, x.rid) for f in (1.0 / 3, 2.0 / 3)] + [x.tg])
     way.setflags(write=False)
     return way
+
+
+LINE_T = 8                    # waypoints per line
+LINE_RULE = (100, 1e-4)       # (max_iterations, stop tolerance) of the line job
+
+
+@functools.lru_cache(maxsize=None)
+def line_goals(c):
+    """(goals [B, 1, 12], far [n]): one goal per problem for the line job, in the reference frame.  Every problem outside `far` takes the
+    case's own target (a near line: the frame at q0 + U(-0.15, 0.15)).  Problem b of far = 1, 4, 7, .. (disjoint from the pushed
+    problems 0, 3, 6, ..) takes the frame at q0[b] + s d[b], d = U(-1.2, 1.2) on the chain's entries, s = 1 halved until the rotation from
+    the start pose to the goal is at most line_common.MAX_ROTATION (log3 near pi is the caller's to split): lines that leave the
+    workspace or the limits and fail on the way.  tests/test_chain_shapes_emulation.py asserts what this draw has to contain."""
+    import line_common
+    import oracle as O
+    x = inputs(c)
+    far = np.arange(1, B, 3)
+    d = np.random.default_rng(SEED + 2).uniform(-1.2, 1.2, (B, x.model.nq)) * x.support
+    start = relative_targets(O, x.om_free, x.q0, x.fid, x.rid)
+    goals = np.array(x.tg)
+    s, todo = np.ones(B), far
+    for _ in range(40):
+        goals[todo] = relative_targets(O, x.om_free, x.q0[todo] + s[todo, None] * d[todo], x.fid, x.rid)
+        angle = line_common.rotation_angle(start[todo, 0, :9].reshape(-1, 3, 3), goals[todo, 0, :9].reshape(-1, 3, 3))
+        todo = todo[angle > line_common.MAX_ROTATION]
+        if todo.size == 0:
+            break
+        s[todo] *= 0.5
+    assert todo.size == 0, (case_id(c), todo)
+    goals.setflags(write=False)
+    far.setflags(write=False)
+    return goals, far
+
+
+@functools.lru_cache(maxsize=None)
+def _twin_model(robot):
+    import twin
+    return twin.load_urdf(robot_xml(robot))
+
+
+@functools.lru_cache(maxsize=None)
+def line_twin_waypoints(c):
+    """[LINE_T, B, 12]: the waypoints of the case's lines by oracle/twin.py (log3, exp3 and FK in numpy) with the case's reference frame."""
+    import line_common
+    x = inputs(c)
+    W = line_common.twin_waypoints(_twin_model(c.robot), c.frame, x.q0, line_goals(c)[0][:, 0], LINE_T, reference=c.reference)
+    W.setflags(write=False)
+    return W
 
 
 MS_K, MS_B = 4, 33     # multi-start / solutions: four supplied starts on 33 problems (132 lanes: two waves and a four-lane tail)

@@ -13,7 +13,8 @@ equal to the oracle's, q within TOL = 1e-6, an iteration-0 stop returns q0 untou
 (T = 3, stop rule and never-stop) equal to three chained dls_batch calls, multi-start and solutions (K = 4 supplied starts on B = 33,
 the near start in slot b % 4 so that the winner moves through the lanes of a group) against their definitions in
 tests/multistart_common.py / tests/solutions_common.py, all by np.array_equal, and the kernel-name queries report the fused kernels;
-(f) the general build of a hot-rtc problem within STEP_BAR of the hot one.
+(f) the general build of a hot-rtc problem within STEP_BAR of the hot one.  The line job has a test function of its own,
+test_line_job_of_every_chain_shape_on_the_device, so that a failure names the job.
 
 A case takes 0.02 - 0.3 s on an MI355X; a hot-rtc case whose program is not in the on-disk cache yet adds its compile (1.2 - 2.3 s
 measured, NJ = 1 .. 7)."""
@@ -166,3 +167,101 @@ def test_chain_shape_on_the_device(torch_cuda, c):
         sols = TS._run(torch, ik_amd, problem, d, Qs, Ts, stop, p100, K, K, SEP, starts, "soa")
         count, _ = SC.check_set(sols, singles, sup, SEP, K, (d.kernel, "solutions"))
         print("%s jobs: multi-start winners %s, solutions by count %s" % (d.kernel, np.bincount(got[3], minlength=K).tolist(), np.bincount(count, minlength=K + 1).tolist()))
+
+
+def _chained_oracle(O, x, W, near, ext=None):
+    """The oracle chained along the waypoints W [T, B, 12] on the lines `near`, a line leaving at its first failed waypoint: per waypoint
+    (alive [n], q, success, iterations)."""
+    prm = O.params(CS.LINE_RULE[0], 1e-2, 1.0, CS.LINE_RULE[1])
+    qo, alive, out = x.q0[near], np.ones(near.size, bool), []
+    for k in range(W.shape[0]):
+        qo, ok_ref, it_ref = O.dls_batch(x.om, x.tasks, np.ascontiguousarray(W[k][near][:, None, :]), qo, prm, ext=ext)
+        out.append((alive, qo, ok_ref, it_ref))
+        alive = alive & (ok_ref == 1)
+    return out
+
+
+@pytest.mark.parametrize("c", CS.CASES, ids=CS.case_id)
+def test_line_job_of_every_chain_shape_on_the_device(torch_cuda, c):
+    """The line job (dls_chain_line_kernel<NJ, KT, SMASK>, and the entry ikgpu_hot_line_stop of the run-time compiled module at
+    NJ = 1 .. 7) on every build of every case: CS.LINE_T waypoints towards CS.line_goals in the case's reference frame under the default
+    stop rule.  Per build: the kernel's name; line_targets against oracle/twin.py with the case's reference at line_common.WAYPOINT_BAR,
+    both layouts giving the same bits and the last waypoint the goal's; dls_line_batch into sentinel-filled outputs np.array_equal to
+    dls_track_batch on line_targets on the written slabs and on `reached`, the sentinels kept elsewhere, both layouts; T = 1 equal to
+    dls_batch to the goal; on the near lines the chained double oracle's flags and iteration counts on every written waypoint and q
+    within 1e-9 on every waypoint met (tests/test_line_emulation.py rule (c)).  A flag or a count that differs from the double oracle
+    is reported with the _Float128 oracle's answer on that line and fails the test: no line is excluded."""
+    torch = torch_cuda
+    import ik_amd
+    import line_common
+    import oracle as O
+    from test_gpu_line import _in_layout, _sentinels
+    x = CS.inputs(c)
+    goals, far = CS.line_goals(c)
+    goals = np.array(goals)
+    q0, B, T, nq = np.array(x.q0), CS.B, CS.LINE_T, x.model.nq
+    near = np.setdiff1d(np.arange(B), far)
+    problem = CS.make_problem(c, x.model)
+    stop, p100 = ik_amd.inverse_kinematics_visitor(CS.LINE_RULE[1]), ik_amd.dls_parameters(max_iterations=CS.LINE_RULE[0])
+    data = _data(problem, general=c.build == "general")
+    assert data.kernel == CS.kernel_name(c, CS.hiprtc_installed()), data.kernel
+    builds = [data]
+    if c.build == "default" and data.kernel.endswith(",hot-rtc>"):
+        builds.append(_data(problem, general=True))
+        assert builds[1].kernel == "dls_chain<NJ=%d,%s,general>" % (c.nj, CS.TYPE_NAMES[c.ktype]), builds[1].kernel
+    Q0 = torch.from_numpy(np.ascontiguousarray(q0.T)).cuda()                          # SoA [nq, B]
+    G = torch.from_numpy(np.ascontiguousarray(goals.transpose(1, 2, 0))).cuda()       # SoA [1, 12, B]
+    W_twin = CS.line_twin_waypoints(c)
+    oracle_at = None
+    for d in builds:
+        assert ik_amd.dls_line_kernel(d, stop, p100) == _variant(d, "_line")
+        W_host = {}
+        for layout in ("soa", "aos"):
+            ql, gl = _in_layout(Q0, G, layout)
+            # the waypoints
+            W = ik_amd.line_targets(problem, ql, gl, d, T, layout=layout)               # [T, 1, 12, B] | [T, B, 1, 12]
+            W_host[layout] = (W[:, 0].permute(0, 2, 1) if layout == "soa" else W[:, :, 0]).cpu().numpy()
+            err = float(np.abs(W_host[layout] - W_twin).max())
+            print("%s %s: max |W_device - W_twin| = %.3g (reference %s)" % (d.kernel, layout, err, c.reference))
+            assert err <= line_common.WAYPOINT_BAR, (d.kernel, layout, err)
+            assert np.array_equal(W_host[layout][T - 1], goals[:, 0]), (d.kernel, layout)
+            # the definition: track on those waypoints
+            Qt, okt, itt = ik_amd.dls_track_batch(problem, ql, W, d, stop, p100, layout=layout)
+            qt = (Qt if layout == "aos" else Qt.permute(0, 2, 1)).cpu().numpy()
+            okt, itt = okt.cpu().numpy(), itt.cpu().numpy()
+            want, _ = line_common.reached_from_flags(okt)
+            mask = line_common.written(want, T)
+            Ql, ok, it, reached = ik_amd.dls_line_batch(problem, ql, gl, d, T, stop, p100, layout=layout, out=_sentinels(torch, T, nq, B, layout))
+            q = (Ql if layout == "aos" else Ql.permute(0, 2, 1)).cpu().numpy()
+            ok, it, reached = ok.cpu().numpy(), it.cpu().numpy(), reached.cpu().numpy()
+            assert np.array_equal(reached, want), (d.kernel, layout)
+            for a, b_, what in ((q, qt, "q"), (ok, okt, "success"), (it, itt, "iterations")):
+                assert np.array_equal(a[mask], b_[mask]), (d.kernel, layout, what)
+            assert np.isnan(q[~mask]).all() and (ok[~mask] == 7).all() and (it[~mask] == -7).all(), (d.kernel, layout)
+            # T = 1: the single solve to the goal
+            q1, ok1, it1 = ik_amd.dls_batch(problem, ql, gl, d, stop, p100, layout=layout)
+            L1 = ik_amd.dls_line_batch(problem, ql, gl, d, 1, stop, p100, layout=layout)
+            for a, b_, what in zip((L1[0][0], L1[1][0], L1[2][0]), (q1, ok1, it1), ("q", "success", "iterations")):
+                assert np.array_equal(a.cpu().numpy(), b_.cpu().numpy()), (d.kernel, layout, "T = 1", what)
+            assert np.array_equal(L1[3].cpu().numpy(), ok1.cpu().numpy().astype(np.int32)), (d.kernel, layout, "T = 1")
+        assert np.array_equal(W_host["aos"], W_host["soa"]), d.kernel
+        # the near lines against the chained oracle (the last layout's q, ok, it: equal to the other's through the definition)
+        if oracle_at is None or not np.array_equal(oracle_at[0], W_host["soa"]):
+            oracle_at = (W_host["soa"], _chained_oracle(O, x, W_host["soa"], near))
+        worst, count, differs = 0.0, np.zeros(near.size, np.int32), np.zeros(near.size, bool)
+        for k, (alive, qo, ok_ref, it_ref) in enumerate(oracle_at[1]):
+            differs |= alive & ((ok[k][near] != ok_ref) | (it[k][near] != it_ref))
+            met = alive & (ok_ref == 1)
+            if met.any():
+                worst = max(worst, float(np.abs(q[k][near][met] - qo[met]).max()))
+            count += met
+        if differs.any():      # a finding: what the _Float128 oracle says on those lines goes into the failure
+            ext = _chained_oracle(O, x, W_host["soa"], near, ext="q")
+            lanes = np.flatnonzero(differs)
+            report = [(int(near[i]), [(int(ok[k][near[i]]), int(it[k][near[i]]), int(oracle_at[1][k][2][i]), int(oracle_at[1][k][3][i]), int(ext[k][2][i]), int(ext[k][3][i]))
+                                      for k in range(T)]) for i in lanes]
+            pytest.fail("%s: near lines differing from the double oracle -- (problem, per waypoint (device ok, it, double ok, it, _Float128 ok, it)): %r" % (d.kernel, report))
+        assert np.array_equal(want[near], count), d.kernel
+        print("%s: reached %s (far lines %s), near lines max |q_line - q_oracle| on met waypoints = %.3g"
+              % (d.kernel, np.bincount(want, minlength=T + 1).tolist(), np.bincount(want[far], minlength=T + 1).tolist(), worst))
+        assert worst <= 1e-9, (d.kernel, worst)

@@ -3,8 +3,9 @@ waypoint, a problem leaving at its first failed waypoint.  The call is DEFINED a
 reference here is ik_amd.dls_track_batch on ik_amd.line_targets and the assertion is np.array_equal on the written slabs and on
 `reached` -- for every build of the chain kernel (one launch: dls_chain_line<...>), both layouts and batch sizes around the wave
 boundary; the slabs beyond a failed waypoint keep their sentinel (the single launch stops there); the waypoints match oracle/twin.py;
-the optional arrays may be null; the launch can be captured; the chained oracle agrees; a tree and a derived-visitor problem run the
-definition inside the call; what has no line is refused.  Inputs: tests/line_common.py."""
+the optional arrays may be null; the launch can be captured; the chained oracle agrees; a tree problem, a derived-visitor problem and
+two-slot problems in a world-fixed reference frame other than the universe run the definition inside the call; what has no line is
+refused.  Inputs: tests/line_common.py.  The other chain lengths, task types, weights and reference frames: tests/test_gpu_chain_shapes.py."""
 import ctypes as C
 
 import numpy as np
@@ -234,14 +235,40 @@ def _workspace_call(torch, ik_amd, problem, data, Q0, G, nT, visitor, short):
     return rc, L.ikgpu_last_error().decode()
 
 
-@pytest.mark.parametrize("kind", ["tree", "derived_visitor"])
+# Two frame tasks in a world-fixed reference frame other than the universe (the waypoint kernel of the other problem kinds reads one
+# reference placement per slot): (robot, URDF text or None for the fixture's, [(frame, type)], reference).  ur5's `base` is rotated by
+# -pi about z against base_link -- far from the identity, yet a symmetric matrix; arm8's `bench` (tests/chain_shapes_common.py) is
+# oblique and displaced, so its transpose is another placement.
+REFERENCE_KINDS = {"reference_base": ("ur5", None, [("tool0", 2), ("wrist_1_link", 0)], "base"),
+                   "reference_bench": ("arm7", "arm8", [("tool", 2), ("l3", 0)], "bench")}
+
+
+@pytest.mark.parametrize("kind", ["tree", "derived_visitor"] + sorted(REFERENCE_KINDS))
 def test_other_problem_kinds_run_the_definition_inside_the_call(torch_cuda, kind):
     torch = torch_cuda
     import ik_amd
     import twin
     from ik_amd import capi
     visitor = None
-    if kind == "tree":
+    if kind in REFERENCE_KINDS:
+        from test_gpu_generic import build
+        import chain_shapes_common as CS
+        name, edited, frames, reference = REFERENCE_KINDS[kind]
+        B, nT = 130, 4
+        xml = CS.arm8_xml() if edited else open(urdf_path(name)).read()
+        _, _, model, problem, data, _, _, q0, tg = build(name, False, [("frame", f, reference, t, 0, None) for f, t in frames], B, seed=0,
+                                                         xml_edit=(lambda _: xml.encode()) if edited else None)
+        assert not data.kernel.startswith("dls_chain"), data.kernel
+        Q0 = torch.from_numpy(np.ascontiguousarray(q0.T)).cuda()
+        G = torch.from_numpy(np.ascontiguousarray(tg.transpose(1, 2, 0))).cuda()
+        W = ik_amd.line_targets(problem, Q0, G, data, nT).permute(0, 3, 1, 2).cpu().numpy()                   # [nT, B, 2, 12]
+        tm = twin.load_urdf(xml)
+        for s, (f, _) in enumerate(frames):
+            err = float(np.abs(W[:, :, s] - line_common.twin_waypoints(tm, f, q0, tg[:, s], nT, reference=reference)).max())
+            print("%s slot %d (%s in %s): max |W_device - W_twin| = %.3g" % (data.kernel, s, f, reference, err))
+            assert err <= line_common.WAYPOINT_BAR, (f, err)
+            assert np.array_equal(W[nT - 1, :, s], tg[:, s])
+    elif kind == "tree":
         from test_gpu_generic import build
         B, nT = 130, 4
         with env(IKGPU_TREE_STATIC_ROWS="0"):
