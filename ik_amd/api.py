@@ -872,6 +872,81 @@ def dls_solutions_batch(problem, Q0, targets, data, visitor=None, p=None, num_st
     return Q, count, which, it
 
 
+def _check_goalset_size(num_goals, num_starts):
+    _check_starts(num_starts)
+    if not isinstance(num_goals, int) or num_goals < 1 or num_goals * num_starts > 64:
+        raise ValueError("the number of goals must be an integer >= 1 with goals x starts <= 64, got %r goals and %r starts" % (num_goals, num_starts))
+
+
+def dls_goalset_kernel(data, visitor=None, p=None, num_goals=4, num_starts=1):
+    """Name of what dls_goalset_batch runs for these parameters: "dls_chain_goalset<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_goalset_kernel(data._h, C.byref(prm), num_goals, num_starts).decode()
+
+
+def dls_goalset_batch(problem, Q0, goals, data, visitor=None, p=None, num_starts=1, seed=0, starts=None, layout="soa", out=None, stream=None):
+    """Reach any of G alternative goals per problem from num_starts starts (G grasp candidates, footholds, docking poses; G =
+    goals.shape[0], G x num_starts <= 64).  Candidate g * num_starts + k is dls_batch from start k (dls_multistart_batch's starts: they do
+    not depend on the goal) against goals[g].  The winner is the first candidate, in that order, that met the stop rule -- the lowest goal
+    index, and within it the lowest start -- else the one with the smallest squared weighted error; Q / success / iterations are
+    bit-identical to dls_batch for that candidate.  reachable[g, b] = 1 where some start of goal g met the stop rule.  A chain problem
+    with G and num_starts powers of two (and G x num_starts >= 2) runs one launch with a problem's candidates in neighbouring lanes.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], goals [G, ntasks, 12, B]   |   "aos": Q0 [B, nq], goals [G, B, ntasks, 12]
+    out: (Q, success uint8 [B], iterations int32 [B], goal int32 [B], start int32 [B], err_sq float64 [B], reachable uint8 [G, B])
+    preallocated, or None.  Returns (Q, success, iterations, goal, start, err_sq, reachable)."""
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
+    if len(Q0.shape) != 2 or len(goals.shape) != 4:
+        raise ValueError("Q0 has shape %s and goals %s, expected 2 and 4 dimensions" % (tuple(Q0.shape), tuple(goals.shape)))
+    G = int(goals.shape[0])
+    _check_goalset_size(G, num_starts)
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(goals.shape[1:]), model.nq, ntasks, B, lay)
+    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
+        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
+    tensors = [Q0, goals] + ([starts] if starts is not None else [])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
+        raise TypeError("dls_goalset_batch needs float64 CUDA tensors")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError("dls_goalset_batch needs contiguous tensors")
+    if any(t.device.index != data._device for t in tensors):
+        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
+    if out is None:
+        Q = torch.empty_like(Q0)
+        ok = torch.empty((B,), dtype=torch.uint8, device=Q0.device)
+        it = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        goal = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        start = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        err = torch.empty((B,), dtype=torch.float64, device=Q0.device)
+        reach = torch.empty((G, B), dtype=torch.uint8, device=Q0.device)
+    else:
+        Q, ok, it, goal, start, err, reach = out
+        _check_tensor("out[0] (Q)", Q, tuple(Q0.shape), torch.float64, data._device)
+        _check_tensor("out[1] (success)", ok, (B,), torch.uint8, data._device)
+        _check_tensor("out[2] (iterations)", it, (B,), torch.int32, data._device)
+        _check_tensor("out[3] (goal)", goal, (B,), torch.int32, data._device)
+        _check_tensor("out[4] (start)", start, (B,), torch.int32, data._device)
+        _check_tensor("out[5] (err_sq)", err, (B,), torch.float64, data._device)
+        _check_tensor("out[6] (reachable)", reach, (G, B), torch.uint8, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_goalset_workspace_bytes(data._h, B, G, num_starts, C.byref(prm))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_goalset_batch(data._h, B, G, num_starts, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
+                                         seed & 0xFFFFFFFFFFFFFFFF, goals.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
+                                         goal.data_ptr(), start.data_ptr(), err.data_ptr(), reach.data_ptr(), lay,
+                                         ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    return Q, ok, it, goal, start, err, reach
+
+
 def _check_tensor(name, t, shape, dtype, device):
     """A device buffer handed to the C ABI as a raw pointer: wrong dtype / device / stride / size would make the kernel read or
     write out of bounds, so it is refused here."""

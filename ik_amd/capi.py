@@ -38,6 +38,7 @@ SYMBOLS = [
     "ikgpu_dls_multistart_batch", "ikgpu_dls_multistart_workspace_bytes", "ikgpu_multistart_starts", "ikgpu_dls_multistart_kernel",
     "ikgpu_dls_solutions_batch", "ikgpu_dls_solutions_workspace_bytes", "ikgpu_dls_solutions_kernel",
     "ikgpu_line_targets", "ikgpu_dls_line_batch", "ikgpu_dls_line_workspace_bytes", "ikgpu_dls_line_kernel",
+    "ikgpu_dls_goalset_batch", "ikgpu_dls_goalset_workspace_bytes", "ikgpu_dls_goalset_kernel",
 ]
 MAX_PIK_LEVELS, MAX_PIK_DA = 8, 128
 
@@ -173,6 +174,13 @@ def lib():
     L.ikgpu_dls_line_workspace_bytes.restype = C.c_size_t
     L.ikgpu_dls_line_kernel.argtypes = [vp, C.POINTER(DlsParams)]
     L.ikgpu_dls_line_kernel.restype = C.c_char_p
+    L.ikgpu_dls_goalset_batch.argtypes = [vp, i64, i32, i32, vp, vp, C.c_uint64, vp, C.POINTER(DlsParams), vp, vp, vp, vp, vp, vp, vp, C.c_int, vp,
+                                          C.c_size_t, vp]
+    L.ikgpu_dls_goalset_batch.restype = C.c_int
+    L.ikgpu_dls_goalset_workspace_bytes.argtypes = [vp, i64, i32, i32, C.POINTER(DlsParams)]
+    L.ikgpu_dls_goalset_workspace_bytes.restype = C.c_size_t
+    L.ikgpu_dls_goalset_kernel.argtypes = [vp, C.POINTER(DlsParams), i32, i32]
+    L.ikgpu_dls_goalset_kernel.restype = C.c_char_p
     L.ikgpu_pik_params_default.argtypes = [C.POINTER(PikParams), i32]
     L.ikgpu_pik_params_default.restype = None
     L.ikgpu_pik_solve_batch.argtypes = [vp, i64, vp, vp, C.POINTER(PikParams), vp, vp, vp, C.c_int, vp]

@@ -808,6 +808,25 @@ int multistart_fused_log2(const ikgpu_problem *p, const ikgpu_dls_params *params
     return l;
 }
 
+// ... and a goal-set kernel when the G x K candidates of a problem are such a group: G and K powers of two, 2 <= G K <= 64.
+bool goalset_fused_log2(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t G, int32_t K, int *log2G, int *log2K) {
+    if (!track_is_fused(p, params) || G < 1 || K < 1 || G > 64 || K > 64 || G * K < 2 || G * K > 64 || (G & (G - 1)) != 0 || (K & (K - 1)) != 0)
+        return false;
+    *log2G = *log2K = 0;
+    while ((1 << *log2G) < G) ++*log2G;
+    while ((1 << *log2K) < K) ++*log2K;
+    return true;
+}
+
+// G goals x K starts per problem, at most 64 candidates.  report: false = the answer only (a query), no message.
+int check_goalset_size(int32_t G, int32_t K, bool report) {
+    const bool bad_g = G < 1 || G > 64, bad_k = K < 1 || K > 64;
+    if (!report) return (bad_g || bad_k || G * K > 64) ? IKGPU_ERR_INVALID : IKGPU_OK;
+    if (int rc = refuse_if(bad_g, "the number of goals must be 1 .. 64")) return rc;
+    if (int rc = check_starts(K)) return rc;
+    return refuse_if(G * K > 64, "goals x starts must be at most 64 candidates per problem");
+}
+
 // What a tracking or multi-start call runs: the fused kernel, "dls_chain<NJ=7,full,hot>" -> "dls_chain_track<NJ=7,full,hot>" for the
 // suffix "_track", or the loop over the single solve.
 std::string variant_kernel_name(const ikgpu_problem *p, bool fused, const char *suffix) {
@@ -1144,6 +1163,71 @@ int ikgpu_dls_solutions_batch(const ikgpu_problem *p, int64_t B, int32_t K, int3
                               const ikgpu::SolutionsInsert m{B, p->host.nq, layout, k, N, sep, p->dev.q_in_chain, q, ok, it, q_sols, count, which, iters};
                               return launched(ikgpu::launch_solutions_insert(m, st), "launching the solution-set insert");
                           });
+    });
+}
+
+const char *ikgpu_dls_goalset_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t G, int32_t K) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    int log2G, log2K;
+    name = variant_kernel_name(p, goalset_fused_log2(p, params, G, K, &log2G, &log2K), "_goalset");
+    return name.c_str();
+}
+
+size_t ikgpu_dls_goalset_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t G, int32_t K, const ikgpu_dls_params *params) {
+    int log2G, log2K;
+    if (!p || !params || B <= 0 || check_goalset_size(G, K, /*report=*/false) || goalset_fused_log2(p, params, G, K, &log2G, &log2K)) return 0;
+    return start_workspace(p, B, /*with_error=*/true).total;
+}
+
+int ikgpu_dls_goalset_batch(const ikgpu_problem *p, int64_t B, int32_t G, int32_t K, const double *q0, const double *starts, uint64_t seed,
+                            const double *goals, const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
+                            int32_t *goal, int32_t *start, double *err_sq, uint8_t *reachable, int layout, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_goalset_size(G, K, /*report=*/true)) return rc;
+    if (int rc = check_layout(layout)) return rc;
+    if (int rc = check_params(params)) return rc;
+    if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
+    if (!q0 || !goals || !q_out) return null_argument();
+    if (int rc = check_launch_size(B, G * K)) return rc;
+    int log2G = 0, log2K = 0;
+    const bool fused = goalset_fused_log2(p, params, G, K, &log2G, &log2K);
+    // (the loop's workspace is refused here, before the device is selected; run_starts checks it again goal by goal)
+    if (!fused && (!workspace || workspace_bytes < start_workspace(p, B, /*with_error=*/true).total))
+        return fail(IKGPU_ERR_INVALID, "goal-set workspace too small: " + std::to_string(workspace ? workspace_bytes : 0) + " bytes given, " +
+                                           std::to_string(start_workspace(p, B, true).total) + " needed (ikgpu_dls_goalset_workspace_bytes)");
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        if (fused) {
+            const ikgpu::BatchIO io{B, q0, goals, q_out, success, iters, layout};
+            ikgpu::ChainJob job{};
+            job.kind = ikgpu::ChainJob::Goalset;
+            job.goal = ikdev::GoalsetArgs{ikdev::MultistartArgs{starts, p->dev.draw, seed, nullptr, err_sq, log2K}, goal, start, reachable, log2G};
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the goal-set DLS kernel");
+        }
+        // every other case: the definition itself, goal after goal and start after start, candidate j = g K + k merged into the caller's
+        // outputs under the multi-start merge's rule with j in place of k (winner = j lands in `goal` when asked for and is split below)
+        const int64_t t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
+        int32_t *winner = goal ? goal : start;
+        for (int g = 0; g < G; ++g) {
+            const double *targets = goals + g * t_slab;
+            const StartsCall c{B, K, q0, starts, seed, targets, params, layout, workspace, workspace_bytes};
+            const int rc = run_starts(p, c, "goal-set", "ikgpu_dls_goalset_workspace_bytes", /*with_error=*/true, st,
+                                      [&](int k, double *q, uint8_t *ok, int32_t *it, double *e, unsigned long long *key) {
+                                          if (const int rc = dispatch_eval(p, B, q, targets, e, nullptr, layout, st)) return rc;
+                                          const ikgpu::MultistartMerge m{B, p->host.nq, p->host.rows, layout, g * K + k, q, e, ok, it, key, q_out, success, iters, winner, err_sq};
+                                          if (const int rc = launched(ikgpu::launch_multistart_merge(m, st), "launching the goal-set merge")) return rc;
+                                          if (!reachable) return static_cast<int>(IKGPU_OK);
+                                          return launched(ikgpu::launch_goalset_reachable(B, k == 0, ok, reachable + static_cast<int64_t>(g) * B, st),
+                                                          "launching the goal-set reachability step");
+                                      });
+            if (rc) {
+                g_last_error = "goal " + std::to_string(g) + ", " + g_last_error;
+                return rc;
+            }
+        }
+        if (!winner) return static_cast<int>(IKGPU_OK);
+        return launched(ikgpu::launch_goalset_split(B, K, winner, goal, start, st), "launching the goal-set index split");
     });
 }
 

@@ -630,6 +630,45 @@ IKD_FN void hot_multistart_body(const ChainKernelArgs<NJ> &a, const MultistartAr
                          [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
 }
 
+// G goals and K starts per problem, the best candidate stored -- dls_chain_goalset_body (chain_kernel_body.hpp: the definition, the lane
+// mapping, the pieces) with the hot program: hot_multistart_lane with the target taken from slab g of the goals.
+template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
+IKD_FN void hot_goalset_lane(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga, const Tab &t, int64_t b, int g, int k, double (&q)[NJ],
+                             bool &success, int &iters, double &err_sq, AnyFn any_active) {
+    multistart_load(a, ga.ms, b, k, q);
+    double raw[12], oMt[12];
+    load_target_raw(a, a.targets + static_cast<int64_t>(g) * 12 * a.B, b, raw);
+    compose_target(a, raw, oMt);
+    hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);
+    double e[6], col[NJ][6];
+    hot_evaluate<NJ, S>(t, q, oMt, e, col);
+    err_sq = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) err_sq = dfma(e[r], e[r], err_sq);
+}
+
+template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn, class Exchange, class Any>
+IKD_FN void hot_goalset_body(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga, const Tab &t, int64_t gid, AnyFn any_active, Exchange exchange,
+                             Any any) {
+    const int log2J = ga.log2G + ga.ms.log2K;
+    const int64_t prob = gid >> log2J;
+    const int j = static_cast<int>(gid & ((int64_t{1} << log2J) - 1));
+    const int g = j >> ga.ms.log2K, k = j & ((1 << ga.ms.log2K) - 1);
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq;
+    bool success;
+    int iters;
+    hot_goalset_lane<NJ, S, NEVERSTOP>(a, ga, t, b, g, k, q, success, iters, err_sq, any_active);
+    const int win = multistart_select(log2J, multistart_key(success, err_sq), j, exchange);
+    const bool reached = any(ga.ms.log2K, success);
+    if (!valid) return;
+    if (ga.reachable && k == 0) ga.reachable[static_cast<int64_t>(g) * a.B + b] = reached ? 1 : 0;
+    if (win == j)
+        goalset_store(a, ga, b, g, k, q, success, iters, err_sq,
+                      [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
+}
+
 // K starts per problem, the distinct converged ones stored -- dls_chain_solutions_body (chain_kernel_body.hpp: the definition, the lane
 // mapping, the three pieces) with the hot program: the unchanged hot_dls, always under a stop rule (without one no start converges).
 template <int NJ, class S, class Tab, class AnyFn>
@@ -714,6 +753,14 @@ __device__ __forceinline__ void hot_multistart_entry(const ChainKernelArgs<NJ> &
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
     hot_multistart_body<NJ, S, NEVERSTOP>(a, ms, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
+}
+
+template <int NJ, class S, bool NEVERSTOP>
+__device__ __forceinline__ void hot_goalset_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const GoalsetArgs &ga) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / (G x K) whole problems
+    HotTable tv;
+    hot_park_table<NJ, S>(t, tv);
+    hot_goalset_body<NJ, S, NEVERSTOP>(a, ga, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{}, GoalsetBallot{});
 }
 
 template <int NJ, class S>

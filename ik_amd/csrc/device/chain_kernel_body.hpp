@@ -7,6 +7,7 @@
 #endif
 
 #include "chain_solver.hpp"
+#include "goalset.hpp"
 #include "line.hpp"
 #include "multistart.hpp"
 #include "solutions.hpp"
@@ -363,6 +364,62 @@ IKD_FN void dls_chain_multistart_body(const ChainKernelArgs<NJ> &a, const Multis
     const int win = multistart_select(ms.log2K, multistart_key(success, err_sq), k, exchange);
     if (valid && win == k)
         multistart_store(a, ms, b, k, q, success, iters, err_sq, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
+}
+
+// ---- goal set: G alternative goals and K starts per problem in one launch, the best candidate stored (include/ikgpu.h
+// ikgpu_dls_goalset_batch) ------------------------------------------------------------------------------------------------------------
+// Defined through the G x K single solves "start k against goal g" (the starts are the multi-start call's and do not depend on the goal;
+// slab g of `a.targets` is what the single solve takes as its targets) and the error ikgpu_evaluate_batch defines at each result.  Lane
+// gid serves problem gid >> (log2G + log2K) with candidate j = the low bits, goal j >> log2K, start j & (K - 1): a problem's candidates
+// are neighbouring lanes of one wave, a goal's K starts neighbours within them.  The key orders (met the stop rule, error, j), so among
+// the candidates that met the stop rule the lowest goal wins and within it the lowest start.  The same three pieces as multi-start, and
+// `any`, the OR over a goal's K lanes, for the reachability flags (device/goalset.hpp GoalsetBallot).
+
+// One candidate: the multi-start lane's code with the target taken from slab g -- load_target in its two halves, the same expressions.
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN void dls_chain_goalset_lane(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga, const Desc &d, int64_t b, int g, int k, double (&q)[NJ],
+                                   bool &success, int &iters, double &err_sq, AnyFn any_active) {
+    constexpr int M = TaskDim<KT>::value;
+    multistart_load(a, ga.ms, b, k, q);
+    double t[12], oMt[12];
+    load_target_raw(a, a.targets + static_cast<int64_t>(g) * 12 * a.B, b, t);
+    compose_target(a, t, oMt);
+    chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active);
+    double e[M], col[NJ][M], Rf[9], pf[3];
+    chain_evaluate<NJ, KT, SMASK>(d, q, oMt, a.prm.idmask, a.prm.unit_weights != 0, e, col, Rf, pf);
+    err_sq = 0.0;
+#pragma unroll
+    for (int r = 0; r < M; ++r) err_sq = dfma(e[r], e[r], err_sq);
+}
+
+// The winning lane's stores: multistart_store (ms.winner is null in a goal-set call) and the winner's two indices.
+template <int NJ, class Pass>
+IKD_FN void goalset_store(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga, int64_t b, int g, int k, const double (&q)[NJ], bool success,
+                          int iters, double err_sq, Pass pass) {
+    multistart_store(a, ga.ms, b, k, q, success, iters, err_sq, pass);
+    if (ga.goal) ga.goal[b] = g;
+    if (ga.start) ga.start[b] = k;
+}
+
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn, class Exchange, class Any>
+IKD_FN void dls_chain_goalset_body(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga, const Desc &d, int64_t gid, AnyFn any_active,
+                                   Exchange exchange, Any any) {
+    const int log2J = ga.log2G + ga.ms.log2K;
+    const int64_t prob = gid >> log2J;
+    const int j = static_cast<int>(gid & ((int64_t{1} << log2J) - 1));
+    const int g = j >> ga.ms.log2K, k = j & ((1 << ga.ms.log2K) - 1);
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq;
+    bool success;
+    int iters;
+    dls_chain_goalset_lane<NJ, KT, SMASK>(a, ga, d, b, g, k, q, success, iters, err_sq, any_active);
+    const int win = multistart_select(log2J, multistart_key(success, err_sq), j, exchange);
+    const bool reached = any(ga.ms.log2K, success);
+    if (!valid) return;
+    if (ga.reachable && k == 0) ga.reachable[static_cast<int64_t>(g) * a.B + b] = reached ? 1 : 0;
+    if (win == j)
+        goalset_store(a, ga, b, g, k, q, success, iters, err_sq, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
 }
 
 // ---- solution set: K starts per problem in one launch, the distinct converged ones stored (include/ikgpu.h ikgpu_dls_solutions_batch) ---

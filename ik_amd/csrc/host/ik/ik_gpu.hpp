@@ -728,6 +728,32 @@ inline void dls_line_device(InverseKinematicsProblem &problem, std::int64_t B, s
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// Any of G alternative goals per problem from K starts on DEVICE buffers (G x K <= 64): candidate g K + k is dls_batch_device from start k
+// (dls_multistart_device's starts) against slab g of goals [G][ntasks][12][B]; the winner is the first candidate that met the stop rule
+// -- the lowest goal, within it the lowest start -- else the one with the smallest squared weighted error, and Q / success / iterations
+// are bit-identical to that solve.  goal / start / err_sq [B] describe the winner; reachable [G][B] is 1 where some start of goal g met the
+// stop rule; each of success .. reachable may be null.  workspace: device memory of goalset_workspace_bytes() bytes (0 for a chain
+// problem with G and K powers of two, G K >= 2: one launch).  Asynchronous on `stream`.
+inline std::size_t goalset_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, int G, int K, dls_data &data,
+                                           const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                           const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_goalset_workspace_bytes(data.handle(), B, G, K, &prm);
+}
+inline void dls_goalset_device(InverseKinematicsProblem &problem, std::int64_t B, int G, int K, const number_t *Q0, const number_t *starts,
+                               std::uint64_t seed, const number_t *goals, dls_data &data, number_t *Q, std::uint8_t *success,
+                               std::int32_t *iterations, std::int32_t *goal, std::int32_t *start, number_t *err_sq, std::uint8_t *reachable,
+                               void *workspace, std::size_t workspace_bytes, void *stream,
+                               const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                               const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_goalset_batch(data.handle(), B, G, K, Q0, starts, seed, goals, &prm, Q, success, iterations, goal, start, err_sq, reachable,
+                                IKGPU_SOA, workspace, workspace_bytes, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // The best of K starts per problem on DEVICE buffers (ik::dls is a local method: ik/ik/dls.cpp:10 "try random walk", dls.cpp:73
 // "perform random restart"; dls_parameters::random_restart, ik/ik/dls.hpp:27, stays inert and ik::dls() is unchanged).  Start 0 is Q0,
 // starts 1 .. K-1 are `starts` [K-1][nq][B] or, when null, generated from `seed`; the winner is the lowest-index start that met the stop

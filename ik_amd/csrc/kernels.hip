@@ -164,6 +164,16 @@ __global__ __launch_bounds__(kBlock) void dls_chain_solutions_kernel(const Chain
                                                    ikdev::SolutionsShuffle{lane & ~((1 << sa.ms.log2K) - 1)});
 }
 
+// G goals and K starts per problem in one launch, the best candidate stored (device/chain_kernel_body.hpp dls_chain_goalset_body): the
+// general build's goal-set kernel.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_goalset_kernel(const ChainKernelArgs<NJ> a, const ikdev::GoalsetArgs ga) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / (G x K) whole problems
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    ikdev::dls_chain_goalset_body<NJ, KT, SMASK>(a, ga, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{},
+                                                 ikdev::GoalsetBallot{});
+}
+
 struct MultistartStartsArgs {
     const double *q0, *lower, *upper;
     const uint8_t *draw;
@@ -200,6 +210,20 @@ __global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m)
     if (m.iters_out) m.iters_out[b] = m.iters[b];
     if (m.winner) m.winner[b] = m.k;
     if (m.err_sq) m.err_sq[b] = err;
+}
+
+__global__ __launch_bounds__(256) void goalset_reachable_kernel(int64_t B, bool first, const uint8_t *success, uint8_t *reachable) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= B) return;
+    reachable[b] = ((first ? 0 : reachable[b]) | success[b]) != 0 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void goalset_split_kernel(int64_t B, int K, const int32_t *winner, int32_t *goal, int32_t *start) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int j = winner[b];   // (read before either store: `winner` is one of the two outputs)
+    if (goal) goal[b] = j / K;
+    if (start) start[b] = j % K;
 }
 
 __global__ __launch_bounds__(256) void solutions_insert(const SolutionsInsert m) {
@@ -312,6 +336,7 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
         else if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
         else if (job.kind == ChainJob::Solutions) hipLaunchKernelGGL((dls_chain_solutions_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.sol);
+        else if (job.kind == ChainJob::Goalset) hipLaunchKernelGGL((dls_chain_goalset_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.goal);
         else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.ms);
         return hipGetLastError();
     });
@@ -521,6 +546,16 @@ hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, i
 
 hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream) {
     hipLaunchKernelGGL(multistart_merge, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_goalset_reachable(int64_t B, bool first, const uint8_t *success, uint8_t *reachable, hipStream_t stream) {
+    hipLaunchKernelGGL(goalset_reachable_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, first, success, reachable);
+    return hipGetLastError();
+}
+
+hipError_t launch_goalset_split(int64_t B, int K, const int32_t *winner, int32_t *goal, int32_t *start, hipStream_t stream) {
+    hipLaunchKernelGGL(goalset_split_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, K, winner, goal, start);
     return hipGetLastError();
 }
 

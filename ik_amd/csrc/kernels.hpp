@@ -8,6 +8,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device/goalset.hpp"
 #include "device/line.hpp"
 #include "device/multistart.hpp"
 #include "device/solutions.hpp"
@@ -82,16 +83,20 @@ struct BatchIO {
 //               (ikgpu_dls_line_batch; dls_chain_line_body, hot_line_body): `io.targets` holds ONE goal per problem, the waypoints are
 //               formed on the lane (device/line.hpp), a problem stops at its first failed waypoint and line.reached counts the ones
 //               before it.  Needs a stop rule, as Solutions.
-// Track, Multistart, Solutions and Line are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
+//   Goalset:    G x K = 1 << (goal.log2G + goal.ms.log2K) candidates per problem in ONE launch, start k against goal g, the best one stored
+//               and each goal's reachability (ikgpu_dls_goalset_batch; dls_chain_goalset_body, hot_goalset_body): `io.targets` holds the G
+//               slabs of goals, B x G x K lanes.
+// Track, Multistart, Solutions, Line and Goalset are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
 // capturable.
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart, Solutions, Line } kind = Solve;
+    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset } kind = Solve;
     int T = 0;                     // Track: the number of waypoints
     ikdev::MultistartArgs ms{};    // Multistart
     ikdev::SolutionsArgs sol{};    // Solutions
     ikdev::LineArgs line{};        // Line
-    int64_t lanes(int64_t B) const {   // one lane per problem, or per start
-        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : B;
+    ikdev::GoalsetArgs goal{};     // Goalset
+    int64_t lanes(int64_t B) const {   // one lane per problem, per start, or per (goal, start)
+        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : B;
     }
 };
 
@@ -130,6 +135,11 @@ struct MultistartMerge {
     double *err_sq;
 };
 hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream);
+// One step of the goal-set definition run as a loop: reachable[b] = (first ? 0 : reachable[b]) | success[b], over the starts of one goal.
+hipError_t launch_goalset_reachable(int64_t B, bool first, const uint8_t *success, uint8_t *reachable, hipStream_t stream);
+// ... and its last: the winning candidate j = winner[b] (which may be `goal` or `start` itself) into goal[b] = j / K, start[b] = j % K;
+// either output may be null.
+hipError_t launch_goalset_split(int64_t B, int K, const int32_t *winner, int32_t *goal, int32_t *start, hipStream_t stream);
 // One step of the solution-set definition run as a loop: start k's single solve (q / success / iters) against the set so far in the
 // caller's outputs -- slots 0 .. count[b]-1 of q_sols.  Inserted into slot count[b] when it succeeded, count[b] < N and some support
 // entry differs by sep or more from every slot; k == 0 initialises count.

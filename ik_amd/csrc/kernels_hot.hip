@@ -55,6 +55,14 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_multistart_kernel(const 
     ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms);
 }
 
+// G goals and K starts per problem in one launch, the best candidate stored (device/chain_hot.hpp hot_goalset_body; include/ikgpu.h
+// ikgpu_dls_goalset_batch): lane gid serves problem gid / (G K) with goal (gid / K) % G and start gid % K.  Lock-step; no LDS, no queue
+// slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_goalset_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::GoalsetArgs ga) {
+    ikdev::hot_goalset_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ga);
+}
+
 // K starts per problem in one launch, the distinct converged ones stored (device/chain_hot.hpp hot_solutions_body; include/ikgpu.h
 // ikgpu_dls_solutions_batch): the multi-start kernel's lane mapping.  Stop rule only; lock-step; no LDS, no queue slot, no allocation.
 template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
@@ -124,6 +132,8 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
             hipLaunchKernelGGL((dls_chain_hot_track_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.T);
         } else if (job.kind == ChainJob::Multistart) {
             hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.ms);
+        } else if (job.kind == ChainJob::Goalset) {
+            hipLaunchKernelGGL((dls_chain_hot_goalset_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.goal);
         } else if (job.kind == ChainJob::Solutions) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (no start converges without a stop rule: the entry point refuses the call)
             else hipLaunchKernelGGL((dls_chain_hot_solutions_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.sol);

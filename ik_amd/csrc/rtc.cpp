@@ -57,6 +57,7 @@
     extern "C" const char sym##_end[];
 IKGPU_EMBED(ikgpu_src_lane_math, "device/lane_math.hpp")
 IKGPU_EMBED(ikgpu_src_chain_solver, "device/chain_solver.hpp")
+IKGPU_EMBED(ikgpu_src_goalset, "device/goalset.hpp")
 IKGPU_EMBED(ikgpu_src_line, "device/line.hpp")
 IKGPU_EMBED(ikgpu_src_multistart, "device/multistart.hpp")
 IKGPU_EMBED(ikgpu_src_solutions, "device/solutions.hpp")
@@ -128,7 +129,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 //       ikdev::<entry><NJ, S<flag>>(a, t<args>);
 //   }
 enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotSolutionsStop, kHotLineStop,
-       kHotEntries };
+       kHotGoalsetNever, kHotGoalsetStop, kHotEntries };
 struct HotEntry {
     const char *name, *params, *entry, *flag, *args;
     bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
@@ -147,11 +148,15 @@ const HotEntry kHotEntryTable[kHotEntries] = {
     {"ikgpu_hot_solutions_stop", ", const ikdev::SolutionsArgs sa", "hot_solutions_entry", "", ", sa", false},
     // a straight Cartesian line to one goal per problem (ikgpu_dls_line_batch): a stop rule always, so one entry
     {"ikgpu_hot_line_stop", ", const ikdev::LineArgs la", "hot_line_entry", "", ", la", false},
+    // G goals and K starts per problem in one launch, the best candidate stored (ikgpu_dls_goalset_batch)
+    {"ikgpu_hot_goalset_never", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", true", ", ga", false},
+    {"ikgpu_hot_goalset_stop", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", false", ", ga", false},
 };
 // The row of a job, or -1: a solution-set or line job has no never-stop entry.
 int hot_entry(ChainJob::Kind kind, bool never) {
     if (kind == ChainJob::Solutions) return never ? -1 : kHotSolutionsStop;
     if (kind == ChainJob::Line) return never ? -1 : kHotLineStop;
+    if (kind == ChainJob::Goalset) return never ? kHotGoalsetNever : kHotGoalsetStop;
     static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
     return first[kind] + (never ? 0 : 1);
 }
@@ -270,6 +275,7 @@ ShapeKey key_of(const ProblemHost &ph) {
 struct Hdr { const char *name, *begin, *end; };
 const Hdr kHeaders[] = {{"lane_math.hpp", ikgpu_src_lane_math, ikgpu_src_lane_math_end},
                         {"chain_solver.hpp", ikgpu_src_chain_solver, ikgpu_src_chain_solver_end},
+                        {"goalset.hpp", ikgpu_src_goalset, ikgpu_src_goalset_end},
                         {"line.hpp", ikgpu_src_line, ikgpu_src_line_end},
                         {"multistart.hpp", ikgpu_src_multistart, ikgpu_src_multistart_end},
                         {"solutions.hpp", ikgpu_src_solutions, ikgpu_src_solutions_end},
@@ -555,21 +561,23 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
             ikdev::MultistartArgs ms;
             ikdev::SolutionsArgs sa;
             ikdev::LineArgs la;
+            ikdev::GoalsetArgs ga;
         } tail;
     } args{};
     constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
     static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8 &&
-                      alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8, "argument layout");
+                      alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8 && alignof(ikdev::GoalsetArgs) == 8, "argument layout");
     constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
                      kBytesTrack = offsetof(Args, tail.T) + sizeof(int),
                      kBytesMultistart = offsetof(Args, tail) + sizeof(ikdev::MultistartArgs), kBytesSolutions = offsetof(Args, tail) + sizeof(ikdev::SolutionsArgs),
-                     kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs);
+                     kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs), kBytesGoalset = offsetof(Args, tail) + sizeof(ikdev::GoalsetArgs);
     static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
     static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
     static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
     static_assert(kBytesMultistart == kHead + sizeof(ikdev::MultistartArgs), "multi-start: the whole of (a, t, ms)");
     static_assert(kBytesSolutions == kHead + sizeof(ikdev::SolutionsArgs), "solution set: the whole of (a, t, sa)");
     static_assert(kBytesLine == kHead + sizeof(ikdev::LineArgs), "line: the whole of (a, t, la)");
+    static_assert(kBytesGoalset == kHead + sizeof(ikdev::GoalsetArgs), "goal set: the whole of (a, t, ga)");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
     fill_chain_kernel_args(a, ph, dt);
     fill_solve_args(a, io, prm);
@@ -591,6 +599,10 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     if (job.kind == ChainJob::Line) {
         args.tail.la = job.line;
         return launch(entry, waves, kBytesLine);
+    }
+    if (job.kind == ChainJob::Goalset) {
+        args.tail.ga = job.goal;
+        return launch(entry, waves, kBytesGoalset);
     }
     if (job.kind == ChainJob::Track) {
         args.tail.T = job.T;

@@ -360,6 +360,44 @@ size_t ikgpu_dls_line_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t
  * waypoint.  The string belongs to the calling thread and lasts until its next call. */
 const char *ikgpu_dls_line_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
 
+/* ---- goal set: reach ANY of G alternative goal poses per problem -- G grasp candidates on an object, G footholds, G docking poses --
+ * from K starts, and learn which goals are reachable at all.  ik::dls is a local method (reference ik/ik/dls.cpp:10 "todo - if limited
+ * convergence, try random walk"; dls.cpp:73 "If issues, perform random restart"; dls_parameters::random_restart, ik/ik/dls.hpp:27, is a
+ * flag nothing reads -- it stays inert here too), and the reference takes one target per task (ik/ik/frame.hpp:189).  G >= 1, K >= 1,
+ * G * K <= 64, else IKGPU_ERR_INVALID.  DEFINED through G * K calls of ikgpu_dls_solve_batch with the same params:
+ *   goals is [G][ntasks x 12 x B]: each slab has the shape, the meaning and the batch layout of the single solve's `targets`;
+ *   the starts are exactly those of ikgpu_dls_multistart_batch and do not depend on the goal: start 0 of problem b is its column of q0;
+ *   start k >= 1 is slab k-1 of `starts` ([K-1][nq x B]) when starts != NULL, else the generated start ikgpu_multistart_starts writes
+ *   for (seed, b, k);
+ *   for candidate j = g * K + k: r_j = (q_j, success_j, iters_j) is what the single solve writes from start k with slab g of `goals` as
+ *   its targets, err_j the sum of squares, in row order, of the M-row weighted error ikgpu_evaluate_batch defines at q_j against slab g;
+ *   the winner is the j with the smallest key (success_j ? 0 : 1, success_j ? 0 : err_j, j): among the candidates that met the stop
+ *   rule the lowest goal index wins and within that goal the lowest start (the caller lists its goals in order of preference, and its
+ *   own start keeps its branch), otherwise the smallest error; a non-finite err_j ranks as +infinity.  Under the never-stop visitor: the
+ *   arg-min of the error over all G * K.
+ * q_out [nq x B], success [B], iters [B] are r_winner bit for bit, over all nq entries (entries outside the support come from the winning
+ * start's own column, clipped once a step was taken, as in multi-start); goal [B] = winner / K, start [B] = winner % K, err_sq [B] =
+ * err_winner; reachable [G][B] (uint8) = 1 if and only if some start of goal g met the stop rule -- all zero under the never-stop
+ * visitor.  success, iters, goal, start, err_sq and reachable may each be NULL.  DEVICE pointers; asynchronous on `stream`; B == 0 is
+ * a no-op.  q_out must not overlap q0, starts or goals.
+ * A chain problem under the reference's visitor with G and K both powers of two and G * K >= 2 runs ONE launch
+ * (`dls_chain_goalset<...>`): lane gid solves problem gid / (G K) from start gid % K against goal (gid / K) % G, the G K lanes of a
+ * group compare their keys across lanes, the winner alone stores, and the first lane of each goal stores its flag (no LDS, no queue
+ * slot, no allocation: capturable in a graph; `workspace` is not read).  Every other case -- tree, generic, static-program and
+ * derived-visitor problems, G or K not a power of two, G = K = 1 -- runs the definition from inside the call, candidate after candidate,
+ * in `workspace` (DEVICE memory of at least ikgpu_dls_goalset_workspace_bytes bytes, else IKGPU_ERR_INVALID); when a step fails,
+ * ikgpu_last_error() names the goal and the start. */
+int ikgpu_dls_goalset_batch(const ikgpu_problem *p, int64_t B, int32_t G, int32_t K, const double *q0, const double *starts, uint64_t seed,
+                            const double *goals, const ikgpu_dls_params *params, double *q_out, uint8_t *success, int32_t *iters,
+                            int32_t *goal, int32_t *start, double *err_sq, uint8_t *reachable, int layout /* ikgpu_layout */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of `workspace` ikgpu_dls_goalset_batch needs for these arguments: 0 for the single launch. */
+size_t ikgpu_dls_goalset_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t G, int32_t K, const ikgpu_dls_params *params);
+/* Name of what ikgpu_dls_goalset_batch runs with these parameters, G and K: `dls_chain_goalset<NJ=7,full,hot>` (or hot-rtc / general:
+ * the build ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the definition run candidate
+ * after candidate.  The string belongs to the calling thread and lasts until its next call. */
+const char *ikgpu_dls_goalset_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t G, int32_t K);
+
 /* FrameTask::target (an SE(3), reference ik/ik/frame.hpp:189) given as 7 doubles -- translation (x y z), quaternion (qx qy qz qw;
  * converted as Eigen's toRotationMatrix does, i.e. as the free-flyer's configuration is read) -- expanded into the 12-double slots
  * the solve entry points take.  pose7: [ntasks x 7 x B] (IKGPU_SOA) or [B x ntasks x 7] (IKGPU_AOS); targets12 likewise with 12.
