@@ -147,6 +147,26 @@ IKD_FN void hot_compose_left(double (&R)[9], double (&p)[3], const Tab &t) {
     }
 }
 
+// The base placement P_0 = (Rc, tc) is constant, and fMt = oMf^-1 oMt = (Rz(q_0) P_1 ... P_NJ)^-1 (P_0^-1 oMt): the target can carry
+// P_0^-1 once per solve instead of the walk composing P_0 in every iteration.  oM0 = P_0^-1 oMt: R' = Rc^T R_t, p' = Rc^T (p_t - tc),
+// with Rc read through hot_rot so that literal 0 / +-1 entries fold as in hot_compose_left.  hot_evaluate<.., BASE_FOLDED = true>
+// takes oM0 where the default form takes oMt; e and the columns see P_0^-1 oMt rounded once, so the two forms differ by rounding.
+// Applied where a lane takes a target (hot_dls at entry, the refill loop's hook), never per iteration.
+template <class S, class Tab>
+IKD_FN void hot_fold_base(const Tab &t, const double (&oMt)[12], double (&oM0)[12]) {
+    double c[9], dp[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c[k] = hot_rot<S, 0>(t, k);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dp[k] = S::tnz(0, k) ? oMt[9 + k] - t.v[S::trans_at(0, k)] : oMt[9 + k];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) oM0[3 * i + j] = dfma(c[i], oMt[j], dfma(c[3 + i], oMt[3 + j], c[6 + i] * oMt[6 + j]));
+        oM0[9 + i] = dfma(c[i], dp[0], dfma(c[3 + i], dp[1], c[6 + i] * dp[2]));
+    }
+}
+
 // e = log6(fMt) (6) and the NEGATED task Jacobian columns col[j] = Jlog6(tMf) J_local(:, j) at q (KT_FULL, unit weights; the
 // reference defines J = -Jlog6 J_local with the frame Jacobian in the LOCAL frame, ik/ik/frame.hpp:162-166).  oMt: target placement
 // in the world.  The chain oMf = P_0 Rz(q_0) P_1 Rz(q_1) ... P_{NJ-1} Rz(q_{NJ-1}) P_NJ is walked from the TIP to the base: the running
@@ -176,7 +196,9 @@ IKD_FN void hot_compose_left(double (&R)[9], double (&p)[3], const Tab &t) {
 // give |phi| = 700 and 2.7e-14.  The folded form's error thus grows with the run's SUM where the unfolded one grew with each joint's own
 // angle.  The second word of 2 pi (dsincos_fast) would not change that: phi_j is a rounded sum, each of its additions is off by up to
 // half an ulp of |phi| (5.5e-17 .. 1.1e-16 |phi|), more than the dropped word's 3.9e-17 |phi|.  So the one-word reduction stays.
-template <int NJ, class S, class Tab>
+// BASE_FOLDED: oMt is hot_fold_base's P_0^-1 oMt and joint 0 -- alone or as the leader of a folded run -- ends the walk with its own
+// rotation, no hot_compose_left<S, 0>.  The columns are read off Y before that composition either way: the same expressions.
+template <int NJ, class S, bool BASE_FOLDED = false, class Tab>
 IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt)[12], double (&e)[6], double (&col)[NJ][6]) {
     constexpr typename ChainRuns<S, NJ>::Table kRuns = ChainRuns<S, NJ>::value;
     // the NJ sin / cos first: independent of the chain, the constants are live once.  A member of a folded run takes phi_j.
@@ -211,7 +233,7 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
             lin[jj][1] = dfma(p[0], R[4], -(p[1] * R[1]));                                                 \
             lin[jj][2] = dfma(p[0], R[5], -(p[1] * R[2]));                                                 \
             rot_z_left(R, p, sn[jj], cs[jj]);                                                              \
-            hot_compose_left<S, jj>(R, p, t);                                                              \
+            if (!(BASE_FOLDED && jj == 0)) hot_compose_left<S, jj>(R, p, t);                               \
             if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }                  \
         } else {                                                                                           \
             /* (R, p) = (R at the run's entry, p~): A lin_j = p~0 (A r1) - p~1 (A r0) once A is known */   \
@@ -231,7 +253,7 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
                 /* the leader: Y is materialised, (R, p) <- P_L Rz(phi_L) (R, p~) */                       \
                 _Pragma("unroll") for (int k = 0; k < 6; ++k) rows[jj][k] = R[k];                          \
                 rot_z_left(R, p, sn[jj], cs[jj]);                                                          \
-                hot_compose_left<S, jj>(R, p, t);                                                          \
+                if (!(BASE_FOLDED && jj == 0)) hot_compose_left<S, jj>(R, p, t);                           \
                 if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }              \
             }                                                                                              \
         }                                                                                                  \
@@ -366,7 +388,8 @@ IKD_FN void hot_step(const Tab &t, const LoopParams &prm, const double (&col)[NJ
     }
 }
 
-// One full solve.  q: in = q0 (chain joints), out = result.  NEVERSTOP: the visitor never stops (stop_sq_tol < 0): every
+// One full solve.  q: in = q0 (chain joints), out = result.  oMt: the target in the world; it is carried into joint 0's frame once, at
+// entry, and every iteration evaluates in the BASE_FOLDED form.  NEVERSTOP: the visitor never stops (stop_sq_tol < 0): every
 // lane takes exactly max_iterations steps.  active: false for a lane that takes no part in this solve (chain_solver.hpp chain_dls).
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
 IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const double (&oMt)[12], int &iters_out,
@@ -374,10 +397,12 @@ IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const 
     constexpr int M = 6;
     bool success = false;
     int iters = prm.max_iterations;
+    double oM0[12];   // the target in joint 0's frame: P_0 leaves the loop (hot_fold_base)
+    hot_fold_base<S>(t, oMt, oM0);
 #pragma unroll 1
     for (int it = 0; it < prm.max_iterations; ++it) {
         double e[M], col[NJ][M];
-        hot_evaluate<NJ, S>(t, q, oMt, e, col);
+        hot_evaluate<NJ, S, true>(t, q, oM0, e, col);
 
         double G[M * M];
         hot_gram<NJ, S>(col, prm.lam2, G);
@@ -442,10 +467,11 @@ IKD_FN void hot_pass_through(const ChainKernelArgs<NJ> &a, int64_t b, bool stepp
 // The hot program under lane refill (chain_kernel_body.hpp chain_refill_loop): the stop-rule mode for batches larger than the machine.
 template <int NJ, class S, class Tab>
 __device__ __forceinline__ void hot_refill_body(const ChainKernelArgs<NJ> &a, const Tab &t, unsigned long long *queue, int chunk) {
+    // (the loop's oMt holds P_0^-1 oMt: folded by the hook below where a lane takes a target, as hot_dls folds at entry -- the same bits)
     chain_refill_loop<NJ>(a, queue, chunk, [&](double (&q)[NJ], const double (&oMt)[12], bool have) {
         constexpr int M = 6;
         double e[M], col[NJ][M];
-        hot_evaluate<NJ, S>(t, q, oMt, e, col);
+        hot_evaluate<NJ, S, true>(t, q, oMt, e, col);
         double G[M * M];
         hot_gram<NJ, S>(col, a.prm.lam2, G);
         double y[M];
@@ -458,16 +484,22 @@ __device__ __forceinline__ void hot_refill_body(const ChainKernelArgs<NJ> &a, co
         const bool stop_now = have && (a.prm.stop_sq_tol >= 0.0) && (e0sq < a.prm.stop_sq_tol);
         hot_step<NJ, S>(t, a.prm, col, y, q, !stop_now);
         return stop_now;
+    }, [&](double (&oMt)[12]) {
+        double w[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) w[k] = oMt[k];
+        hot_fold_base<S>(t, w, oMt);
     });
 }
 #endif
 
 // B independent ik::dls() calls, lane `gid`: load, solve, store -- dls_chain_body (chain_kernel_body.hpp) with the hot program.
+// wave_start: the measurement build's stamp of the kernel's first instruction (hot_kernel_entry); unused otherwise.
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
-IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t gid, AnyFn any_active) {
+IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t gid, AnyFn any_active, long long wave_start = 0) {
     const ChainStrides st = chain_strides(a);
 #if defined(IKGPU_HOT_STAMP) && IKD_ON_DEVICE
-    const long long rs = wall_clock64();   // wave start, 100 MHz ticks
+    const long long rs = wave_start;   // wave start, 100 MHz ticks
 #endif
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
@@ -606,8 +638,9 @@ IKD_FN void hot_multistart_lane(const ChainKernelArgs<NJ> &a, const MultistartAr
     double oMt[12];
     load_target(a, b, oMt);
     hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);
-    double e[6], col[NJ][6];
-    hot_evaluate<NJ, S>(t, q, oMt, e, col);
+    double e[6], col[NJ][6], oM0[12];
+    hot_fold_base<S>(t, oMt, oM0);   // (hot_dls's own fold again: the same values, and P_0 stays out of the loop's live registers)
+    hot_evaluate<NJ, S, true>(t, q, oM0, e, col);
     err_sq = 0.0;
 #pragma unroll
     for (int r = 0; r < 6; ++r) err_sq = dfma(e[r], e[r], err_sq);
@@ -640,8 +673,9 @@ IKD_FN void hot_goalset_lane(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga
     load_target_raw(a, a.targets + static_cast<int64_t>(g) * 12 * a.B, b, raw);
     compose_target(a, raw, oMt);
     hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);
-    double e[6], col[NJ][6];
-    hot_evaluate<NJ, S>(t, q, oMt, e, col);
+    double e[6], col[NJ][6], oM0[12];
+    hot_fold_base<S>(t, oMt, oM0);   // (hot_dls's own fold again: the same values, and P_0 stays out of the loop's live registers)
+    hot_evaluate<NJ, S, true>(t, q, oM0, e, col);
     err_sq = 0.0;
 #pragma unroll
     for (int r = 0; r < 6; ++r) err_sq = dfma(e[r], e[r], err_sq);
@@ -725,10 +759,21 @@ __device__ __forceinline__ void hot_park_table(const HotTable &t, HotTable &tv) 
 
 template <int NJ, class S, bool NEVERSTOP>
 __device__ __forceinline__ void hot_kernel_entry(const ChainKernelArgs<NJ> &a, const HotTable &t) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
+#if defined(IKGPU_HOT_STAMP)
+    // measurement build: the wave's first stamp, as early as the compiler lets it stand.  The workgroup index passes through the
+    // statement, so every per-lane address -- every load from HBM -- comes after it; the kernel-argument loads do not depend on it and
+    // the compiler issues the first batch of them ahead (the listing says how many instructions and waits stand in front).
+    long long wave_start;
+    unsigned block = blockIdx.x;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wave_start), "+s"(block) : : "memory");
+#else
+    const long long wave_start = 0;
+    const unsigned block = blockIdx.x;
+#endif
+    const int64_t gid = static_cast<int64_t>(block) * 64 + threadIdx.x;   // one wave64 per workgroup
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
-    hot_chain_body<NJ, S, NEVERSTOP>(a, tv, gid, KeepGoing{a.leave_active, a.leave_after, 0});
+    hot_chain_body<NJ, S, NEVERSTOP>(a, tv, gid, KeepGoing{a.leave_active, a.leave_after, 0}, wave_start);
 }
 
 template <int NJ, class S, bool NEVERSTOP>

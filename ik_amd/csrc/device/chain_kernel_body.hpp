@@ -499,8 +499,14 @@ IKD_FN void dls_chain_solutions_body(const ChainKernelArgs<NJ> &a, const Solutio
 // queue[0]: head -- problems handed out (in chunks) beyond the first (static) round, queue[1]: waves that have left; the last wave out
 // zeroes both, so the next launch on the same stream finds the slot clean (host: QueuePool in kernels.hpp).
 // iterate(q, oMt, have) runs ONE iteration of this lane's problem in place and returns "the visitor stopped it before the step".
-template <int NJ, class IterFn>
-__device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, unsigned long long *queue, int chunk_and_batch, IterFn iterate) {
+// on_target(oMt) is called once where a lane takes a target -- the first round and every refill --, in place: the hot program carries the
+// target into joint 0's frame there (chain_hot.hpp hot_fold_base); the default does nothing.
+struct KeepTarget {
+    __device__ __forceinline__ void operator()(double (&)[12]) const {}
+};
+template <int NJ, class IterFn, class TargetFn = KeepTarget>
+__device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, unsigned long long *queue, int chunk_and_batch, IterFn iterate,
+                                                  TargetFn on_target = TargetFn{}) {
     const ChainStrides st = chain_strides(a);
     const int lane = static_cast<int>(threadIdx.x) & 63;                 // one wave per workgroup
     const int64_t first_round = static_cast<int64_t>(gridDim.x) * 64;
@@ -524,6 +530,7 @@ __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(st.elem, st.q_prob, a.qidx[j], b)];
     load_target(a, b, oMt);
+    on_target(oMt);
     if (listed) it = a.iters[b];                                         // (the iterations the first phase took over this problem)
     // The wave's own reserve [pool_lo, pool_hi) of unsolved problems (wave-uniform): finished lanes are served from it, and only when
     // it runs dry does the wave pull `chunk` (>= 64) more from the launch's head.  One atomic per finished LANE-GROUP on one address
@@ -574,6 +581,7 @@ __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, 
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(st.elem, st.q_prob, a.qidx[j], b)];
                 load_target(a, b, oMt);
+                on_target(oMt);
                 it = listed ? a.iters[b] : 0;
             }
         }

@@ -45,3 +45,27 @@ wg = np.arange(ticks.size)
 print("by XCD (workgroup index mod 8): loop us " + " ".join("%.2f" % ticks[wg % 8 == x].mean() for x in range(8)))
 print("by XCD: loop cycles " + " ".join("%.0f" % cyc[wg % 8 == x].mean() for x in range(8)))
 print("by XCD: end tick - first start (us) " + " ".join("%.2f" % ((t_end[wg % 8 == x].max() - t_start.min()) / 100) for x in range(8)))
+
+# What a step pays OUTSIDE every wave's stamped span, from the stamps alone: six launches back to back on one stream, each into buffers
+# of its own.  The wave-start stamp is taken at the kernel's entry (hot_kernel_entry), so the period from one launch's first start to
+# the next one's is the step time, and period - span is the time between a launch's last wave end (stores acknowledged) and the next
+# launch's first instruction: the end-of-kernel release, the dispatch of the next grid and the wave launch.  The stamps are 100 MHz ticks
+# of the device's own counter; a kernel trace's begin and end are the runtime's translation of the packet processor's timestamps into
+# nanoseconds of the host clock, and nothing here ties the two scales together, so how the gap splits into "after the last wave" and
+# "before the first" stays open.
+outs = [None] * 6
+for k in range(len(outs)):
+    outs[k] = ik_amd.dls_batch(problem, Q0, T, data, ik_amd.never_stop_visitor(), p, out=outs[k])
+torch.cuda.synchronize()
+first, last = [], []
+for o in outs:
+    s = o[2].cpu().numpy().reshape(-1, 64)
+    a, b = s[:, 4].astype(np.int64), s[:, 5].astype(np.int64)
+    first.append(a.min())
+    last.append(b.max())
+first, last = np.array(first), np.array(last)
+span, period = (last - first) / 100.0, np.diff(first) / 100.0
+gap = (first[1:] - last[:-1]) / 100.0
+print("six launches back to back: span (first start -> last end) us " + " ".join("%.2f" % v for v in span))
+print("  period (first start -> next first start) us " + " ".join("%.2f" % v for v in period))
+print("  gap (last end -> next first start) us " + " ".join("%.2f" % v for v in gap) + "; mean of the last four %.2f" % gap[1:].mean())
