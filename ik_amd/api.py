@@ -709,6 +709,99 @@ def dls_line_batch(problem, Q0, goals, data, T, visitor=None, p=None, layout="so
     return Q, ok, it, reached
 
 
+def _check_path_inputs(who, Q0, vias, model, ntasks, lay, data):
+    """_check_line_inputs for (Q0, vias): vias is P slabs of what the line entries take as goals.  Returns (B, P)."""
+    if len(Q0.shape) != 2 or len(vias.shape) != 4:
+        raise ValueError("Q0 has shape %s and vias %s, expected 2 and 4 dimensions (via poses outermost)" % (tuple(Q0.shape), tuple(vias.shape)))
+    if vias.shape[0] < 1:
+        raise ValueError("vias holds no via pose (P must be at least 1)")
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(vias.shape[1:]), model.nq, ntasks, B, lay)
+    import torch
+    if not (isinstance(Q0, torch.Tensor) and isinstance(vias, torch.Tensor) and Q0.is_cuda and vias.is_cuda
+            and Q0.dtype == torch.float64 and vias.dtype == torch.float64):
+        raise TypeError("%s needs float64 CUDA tensors" % who)
+    if not (Q0.is_contiguous() and vias.is_contiguous()):
+        raise ValueError("%s needs contiguous tensors" % who)
+    if Q0.device.index != data._device or vias.device.index != data._device:
+        raise ValueError("tensors live on cuda:%s / cuda:%s but the problem was created on device %d"
+                         % (Q0.device.index, vias.device.index, data._device))
+    return B, vias.shape[0]
+
+
+def path_targets(problem, Q0, vias, data, T, layout="soa"):
+    """The P x T waypoints of the Cartesian path through P via poses per problem (include/ikgpu.h ikgpu_path_targets): segment 0 is
+    line_targets(problem, Q0, vias[0], data, T); segment s >= 1 runs from via s - 1's own twelve values to via s; waypoint s T + T - 1 is
+    via s itself.  The slot restrictions are line_targets'.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], vias [P, ntasks, 12, B]   |   "aos": Q0 [B, nq], vias [P, B, ntasks, 12].
+    Returns W [P T, ntasks, 12, B] | [P T, B, ntasks, 12], the shape of dls_track_batch's targets."""
+    import torch
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    _check_waypoints(T)
+    B, P = _check_path_inputs("path_targets", Q0, vias, model, ntasks, lay, data)
+    W = torch.empty((P * T,) + tuple(vias.shape[1:]), dtype=torch.float64, device=Q0.device)
+    data._bind(problem)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream
+    capi.check(capi.lib().ikgpu_path_targets(data._h, B, P, T, Q0.data_ptr(), vias.data_ptr(), W.data_ptr(), lay, C.c_void_p(s)))
+    return W
+
+
+def dls_path_kernel(data, visitor=None, p=None):
+    """Name of what dls_path_batch runs for these parameters: "dls_chain_path<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_path_kernel(data._h, C.byref(prm)).decode()
+
+
+def dls_path_batch(problem, Q0, vias, data, T, max_joint_step=0.0, visitor=None, p=None, layout="soa", out=None, stream=None):
+    """Can the task frame travel from where it is at Q0 through its P via poses, T waypoints per segment, without a joint-space jump --
+    and along which joint trajectory?  dls_track_batch on path_targets(problem, Q0, vias, data, T), a problem taking part in waypoint n
+    only while all its earlier waypoints were met: the solve met the stop rule and, with max_joint_step > 0, no entry of the task
+    support moved by more than max_joint_step (rad, plain entries) from the configuration the solve started from.  reached[b] counts
+    the waypoints met before the first one that was not (P T: the whole path); slabs n <= min(reached[b], P T - 1) of problem b are
+    written and bit-identical to dls_track_batch on those waypoints, later slabs are unspecified; success = 1 in the failing slab says
+    the waypoint was reached through a jump.  A chain problem runs one launch that reads the P vias alone.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], vias [P, ntasks, 12, B]   |   "aos": Q0 [B, nq], vias [P, B, ntasks, 12].
+    out: (Q [P T, nq, B] | [P T, B, nq], success uint8 [P T, B], iterations int32 [P T, B], reached int32 [B]) preallocated, or None.
+    Returns (Q, success, iterations, reached)."""
+    import math
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    _check_waypoints(T)
+    if not isinstance(max_joint_step, (int, float)) or not math.isfinite(max_joint_step) or max_joint_step < 0:
+        raise ValueError("max_joint_step must be finite and not negative (0: no joint-step rule), got %r" % (max_joint_step,))
+    B, P = _check_path_inputs("dls_path_batch", Q0, vias, model, ntasks, lay, data)
+    N = P * T
+    q_shape = (N, model.nq, B) if lay == capi.SOA else (N, B, model.nq)
+    if out is None:
+        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
+        ok = torch.empty((N, B), dtype=torch.uint8, device=Q0.device)
+        it = torch.empty((N, B), dtype=torch.int32, device=Q0.device)
+        reached = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+    else:
+        Q, ok, it, reached = out
+        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
+        _check_tensor("out[1] (success)", ok, (N, B), torch.uint8, data._device)
+        _check_tensor("out[2] (iterations)", it, (N, B), torch.int32, data._device)
+        _check_tensor("out[3] (reached)", reached, (B,), torch.int32, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_path_workspace_bytes(data._h, B, P, T, C.byref(prm))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_path_batch(data._h, B, P, T, Q0.data_ptr(), vias.data_ptr(), C.byref(prm), float(max_joint_step), Q.data_ptr(), ok.data_ptr(),
+                                      it.data_ptr(), reached.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    return Q, ok, it, reached
+
+
 def dls_multistart_kernel(data, visitor=None, p=None, num_starts=8):
     """Name of what dls_multistart_batch runs for these parameters: "dls_chain_multistart<...>" (one launch) or "loop(<data.kernel>)"."""
     prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())

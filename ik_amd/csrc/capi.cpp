@@ -1068,6 +1068,104 @@ int ikgpu_dls_line_batch(const ikgpu_problem *p, int64_t B, int64_t T, const dou
     });
 }
 
+}  // extern "C"
+
+namespace {
+
+// What the path entry points share with the line's, and P segments: P >= 1, T >= 0, P T waypoints in a 32-bit count.
+int check_path_call(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, int layout) {
+    if (int rc = check_line_call(p, B, T, layout)) return rc;
+    if (int rc = refuse_if(P < 1, "the number of via poses must be at least 1")) return rc;
+    return refuse_if(T > 0 && P > 0x7fffffff / T, "too many waypoints for one call (P x T must fit 31 bits)");
+}
+
+// ikgpu_path_targets for validated arguments, inside on_device.
+int dispatch_path_targets(const ikgpu_problem *p, int64_t B, int P, int T, const double *q0, const double *vias, double *W, int layout, hipStream_t st) {
+    if (p->host.kind == ikgpu::KernelKind::Chain)
+        return launched(ikgpu::launch_path_targets_chain(p->host, p->dev, B, P, T, q0, vias, W, layout, st), "launching the path waypoint kernel");
+    // every other kind: oMf(q0) of every slot into slab 0, then the waypoints over it (dispatch_line_targets)
+    const hipError_t e = p->host.kind == ikgpu::KernelKind::Tree && !p->host.tree_extras()
+                             ? ikgpu::launch_eval_tree(p->host, p->dev, B, q0, q0, nullptr, nullptr, W, layout, st)
+                             : ikgpu::launch_eval_generic(p->gen, p->dev, B, q0, q0, nullptr, nullptr, W, layout, st);
+    if (e != hipSuccess) return hip_fail(e, "launching the FK kernel");
+    return launched(ikgpu::launch_path_targets_from_fk(B, p->gen.ntasks, P, T, p->dev.g_dbls + p->gen.generic.o_trpl, vias, W, layout, st),
+                    "launching the path waypoint kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int ikgpu_path_targets(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const double *q0, const double *vias, double *W_out, int layout,
+                       void *stream) {
+    if (int rc = check_path_call(p, B, P, T, layout)) return rc;
+    if (B == 0 || T == 0) return IKGPU_OK;  // nothing to write (the pointers may be null; the problem is not looked at)
+    if (!q0 || !vias || !W_out) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
+    if (int rc = check_line_slots(p)) return rc;
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        return dispatch_path_targets(p, B, static_cast<int>(P), static_cast<int>(T), q0, vias, W_out, layout, st);
+    });
+}
+
+const char *ikgpu_dls_path_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    name = variant_kernel_name(p, track_is_fused(p, params), "_path");
+    return name.c_str();
+}
+
+size_t ikgpu_dls_path_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const ikgpu_dls_params *params) {
+    if (!p || !params || B <= 0 || T <= 0 || P < 1 || P > 0x7fffffff / T || track_is_fused(p, params)) return 0;
+    return line_workspace(p, B, P * T).total;   // the line loop's carving over P T waypoints: the waypoints, then the flags
+}
+
+int ikgpu_dls_path_batch(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const double *q0, const double *vias,
+                         const ikgpu_dls_params *params, double max_joint_step, double *q_traj, uint8_t *success, int32_t *iters,
+                         int32_t *reached, int layout, void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = check_path_call(p, B, P, T, layout)) return rc;
+    if (int rc = check_params(params)) return rc;
+    if (!(max_joint_step >= 0.0) || !std::isfinite(max_joint_step))
+        return fail(IKGPU_ERR_INVALID, "max_joint_step must be finite and not negative (0: no joint-step rule)");
+    if (params->stop_sq_tol < 0.0 && !ikgpu::visitor_extended(*params))
+        return fail(IKGPU_ERR_INVALID, "the never-stop visitor reaches no waypoint: a path needs a stop rule (stop_sq_tol >= 0)");
+    if (B == 0 || T == 0) return IKGPU_OK;  // nothing to solve (the pointers may be null; the problem is not looked at)
+    if (!q0 || !vias || !q_traj) return null_argument();
+    if (int rc = check_launch_size(B)) return rc;
+    if (int rc = check_line_slots(p)) return rc;
+    const int64_t N = P * T;
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        if (track_is_fused(p, params)) {
+            const ikgpu::BatchIO io{B, q0, vias, q_traj, success, iters, layout};
+            ikgpu::ChainJob job{};
+            job.kind = ikgpu::ChainJob::Path;
+            job.path = ikdev::PathArgs{reached, static_cast<int>(T), static_cast<int>(P), max_joint_step};
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the DLS path kernel");
+        }
+        // every other kind: the definition itself -- the waypoints, the chained calls, the met rule over flags and joint steps
+        const LineWorkspace w = line_workspace(p, B, N);
+        if (!workspace || workspace_bytes < w.total)
+            return fail(IKGPU_ERR_INVALID, "path workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                               std::to_string(w.total) + " needed (ikgpu_dls_path_workspace_bytes)");
+        char *ws = static_cast<char *>(workspace);
+        double *W = reinterpret_cast<double *>(ws + w.targets);
+        uint8_t *ok = success ? success : reinterpret_cast<uint8_t *>(ws + w.success);
+        if (const int rc = dispatch_path_targets(p, B, static_cast<int>(P), static_cast<int>(T), q0, vias, W, layout, st)) return rc;
+        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B, t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
+        for (int64_t n = 0; n < N; ++n) {
+            const ikgpu::BatchIO io{B, n == 0 ? q0 : q_traj + (n - 1) * q_slab, W + n * t_slab, q_traj + n * q_slab, ok + n * B,
+                                    iters ? iters + n * B : nullptr, layout};
+            if (const int rc = dispatch_dls(p, io, params, st)) {
+                g_last_error = "waypoint " + std::to_string(n) + ": " + g_last_error;
+                return rc;
+            }
+        }
+        if (!reached) return static_cast<int>(IKGPU_OK);
+        const ikgpu::PathReached r{B, p->host.nq, static_cast<int>(N), layout, max_joint_step, p->dev.q_in_chain, ok, q0, q_traj, reached};
+        return launched(ikgpu::launch_path_reached(r, st), "launching the path count");
+    });
+}
+
 const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
     if (!p || !params) return "";
     thread_local std::string name;

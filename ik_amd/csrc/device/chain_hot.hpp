@@ -628,6 +628,58 @@ IKD_FN int hot_line_body(const ChainKernelArgs<NJ> &a, const Tab &t, const LineA
     return k;
 }
 
+// A Cartesian path through P vias per problem with the joint-step rule -- dls_chain_path_body (chain_kernel_body.hpp: the definition, the
+// met rule, the lane's order of work, which slabs are written) with the hot program.  Between waypoints the lane parks q and q_prev
+// (2 NJ doubles), the segment's start pose, its rotation vector and the current via (27 doubles); via s + 1 (twelve more) is in flight
+// during the last solve of segment s only and consumed right after it, in front of that waypoint's stores.
+template <int NJ, class S, class Tab, class AnyFn>
+IKD_FN int hot_path_body(const ChainKernelArgs<NJ> &a, const Tab &t, const PathArgs &pa, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
+    const bool valid = gid < a.B;
+    const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
+    double q[NJ], q_prev[NJ], via[12], next[12];
+    line_load(a, b, q, via);
+    LineStart ls;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
+    line_chain_start(a, *(ConstDesc *)a.desc, q, via, ls);
+    bool alive = true, stepped = false;
+    int reached = 0;
+    int64_t n = 0;
+    for (int s = 0; s < pa.P && IKD_ANY(alive); ++s) {
+        for (int k = 0; k < pa.T && IKD_ANY(alive); ++k, ++n) {
+            double w[12], oMt[12];
+            line_waypoint(ls, via, k, pa.T, w);
+            compose_target(a, w, oMt);
+            const bool turn = k + 1 == pa.T && s + 1 < pa.P;   // the last waypoint of a segment that has a successor
+            if (turn) load_target_raw(a, a.targets + (s + 1) * t_slab, b, next);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_prev[j] = q[j];
+            int iters;
+            bool success;
+            hot_dls<NJ, S, false>(t, a.prm, q, oMt, iters, success, any_active, alive);   // (any_active by value: a fresh count per waypoint)
+            if (turn) {
+                line_start_from_pose(via, next, ls);
+#pragma unroll
+                for (int c = 0; c < 12; ++c) via[c] = next[c];
+            }
+            stepped = stepped || (alive && iters > 0);
+            if (valid && alive) {
+                double *q_out = a.q_out + n * q_slab;
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
+                if (a.success) a.success[n * a.B + b] = success ? 1 : 0;
+                if (a.iters) a.iters[n * a.B + b] = iters;
+                hot_pass_through_to(a, q_out, b, stepped);
+            }
+            alive = alive && success && !path_jumped<NJ>(q, q_prev, pa.max_joint_step);
+            reached += alive ? 1 : 0;
+        }
+    }
+    if (valid && pa.reached) pa.reached[b] = reached;
+    return static_cast<int>(n);
+}
+
 // K starts per problem, the best one stored -- dls_chain_multistart_body (chain_kernel_body.hpp: the definition, the lane mapping, the
 // three pieces) with the hot program: the unchanged hot_dls, then one more hot_evaluate at its result for the error alone (its Jacobian
 // columns are dead code).
@@ -790,6 +842,14 @@ __device__ __forceinline__ void hot_line_entry(const ChainKernelArgs<NJ> &a, con
     HotTable tv;
     hot_park_table<NJ, S>(t, tv);
     (void)hot_line_body<NJ, S>(a, tv, la, gid, KeepGoing{0, 0, 0});
+}
+
+template <int NJ, class S>
+__device__ __forceinline__ void hot_path_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const PathArgs &pa) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
+    HotTable tv;
+    hot_park_table<NJ, S>(t, tv);
+    (void)hot_path_body<NJ, S>(a, tv, pa, gid, KeepGoing{0, 0, 0});
 }
 
 template <int NJ, class S, bool NEVERSTOP>

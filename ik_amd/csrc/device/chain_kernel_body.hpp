@@ -279,6 +279,70 @@ IKD_FN int dls_chain_line_body(const ChainKernelArgs<NJ> &a, const Desc &d, cons
     return k;
 }
 
+// ---- path: a Cartesian path through P via poses per problem, T waypoints per segment, with a joint-step rule (include/ikgpu.h
+// ikgpu_dls_path_batch) ----------------------------------------------------------------------------------------------------------------
+// Defined as the tracking call on the P x T waypoints of ikgpu_path_targets: segment 0 is the line above (from the pose at q0 to via 0),
+// segment s >= 1 runs from via s - 1's own twelve values to via s (line_start_from_pose).  A problem takes part in waypoint n = s T + k
+// only while all its earlier waypoints were MET: the solve met the stop rule and, with max_joint_step > 0, no chain entry moved by
+// more than max_joint_step from the configuration the solve started from (path_jumped: q0 for n = 0, the result of waypoint n - 1
+// after that).  a.targets holds the P slabs of vias.  Between waypoints the lane parks q, q_prev (NJ entries each), the segment's start
+// pose, its rotation vector and the current via; the twelve loads of via s + 1 are issued before the LAST solve of segment s and
+// consumed right after it, in front of that waypoint's stores -- no load waits between two solves and no store stands in front of the
+// wait (hot_track_body's order).  Dead lanes, the written slabs and the entries of q outside the chain: as the line body; the failing
+// slab carries the solve's own flag, so success = 1 there says "reached, but through a jump".
+// Returns the waypoints this lane's wave went through (the host-side lane emulator reads it; a kernel ignores it).
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN int dls_chain_path_body(const ChainKernelArgs<NJ> &a, const Desc &d, const PathArgs &pa, int64_t gid, AnyFn any_active) {
+    const ChainStrides st = chain_strides(a);
+    const bool valid = gid < a.B;
+    const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
+    double q[NJ], q_prev[NJ], via[12], next[12];
+    line_load(a, b, q, via);
+    LineStart ls;
+    line_chain_start(a, d, q, via, ls);
+    bool alive = true, stepped = false;
+    int reached = 0;
+    int64_t n = 0;
+    for (int s = 0; s < pa.P && IKD_ANY(alive); ++s) {
+        for (int k = 0; k < pa.T && IKD_ANY(alive); ++k, ++n) {
+            double t[12], oMt[12];
+            line_waypoint(ls, via, k, pa.T, t);
+            compose_target(a, t, oMt);
+            const bool turn = k + 1 == pa.T && s + 1 < pa.P;   // the last waypoint of a segment that has a successor
+            if (turn) load_target_raw(a, a.targets + (s + 1) * t_slab, b, next);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_prev[j] = q[j];
+            int iters;
+            bool success;
+            chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active, alive);   // (any_active by value: a fresh count per waypoint)
+            if (turn) {
+                line_start_from_pose(via, next, ls);
+#pragma unroll
+                for (int c = 0; c < 12; ++c) via[c] = next[c];
+            }
+            stepped = stepped || (alive && iters > 0);
+            if (valid && alive) {
+                double *q_out = a.q_out + n * q_slab;
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
+                if (a.success) a.success[n * a.B + b] = success ? 1 : 0;
+                if (a.iters) a.iters[n * a.B + b] = iters;
+                for (int i = 0; i < a.nq; ++i) {
+                    if (a.q_in_chain[i]) continue;
+                    const double v = a.q0[at(st.elem, st.q_prob, i, b)];
+                    const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
+                    q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
+                }
+            }
+            alive = alive && success && !path_jumped<NJ>(q, q_prev, pa.max_joint_step);
+            reached += alive ? 1 : 0;
+        }
+    }
+    if (valid && pa.reached) pa.reached[b] = reached;
+    return static_cast<int>(n);
+}
+
 // ---- multi-start: K starts per problem in one launch, the best one stored (include/ikgpu.h ikgpu_dls_multistart_batch) ----------------
 // Defined through K calls of the single solve from K starts (start 0: the caller's q0; start k >= 1: slab k - 1 of the caller's
 // `starts`, or drawn from the seed -- device/multistart.hpp) and the error ikgpu_evaluate_batch defines at each result; ik::dls is a

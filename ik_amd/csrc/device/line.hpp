@@ -1,5 +1,7 @@
 // line.hpp -- the waypoints of a straight Cartesian line (include/ikgpu.h ikgpu_line_targets, ikgpu_dls_line_batch): the start pose of
-// a task frame in its reference frame, the rotation logarithm and exponential, and waypoint k of T between the start and the goal.
+// a task frame in its reference frame, the rotation logarithm and exponential, and waypoint k of T between the start and the goal --
+// and of a path through via poses (ikgpu_path_targets, ikgpu_dls_path_batch): the start of a later segment from the previous via, the
+// path kernels' arguments and the joint-step test.
 //
 // ONE source of this arithmetic: the kernels behind ikgpu_line_targets (kernels.hip) and the fused line bodies (dls_chain_line_body in
 // chain_kernel_body.hpp, hot_line_body in chain_hot.hpp) call the functions below and nothing else, which is what makes the fused launch
@@ -109,6 +111,39 @@ IKD_FN void line_start(RefPtr ref, const double (&Rf)[9], const double (&pf)[3],
 #pragma unroll
         for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = dfma(s.R0[i], goal[j], dfma(s.R0[3 + i], goal[3 + j], s.R0[6 + i] * goal[6 + j]));
     log3(Rrel, s.w);
+}
+
+// The start of a segment from a GIVEN pose -- segment s >= 1 of a path (include/ikgpu.h ikgpu_path_targets) starts at via s - 1's own
+// twelve values: (R0, p0) = from, w = log3(R0^T R1), the last product of line_start in the same expressions.  The one source for the
+// kernels behind ikgpu_path_targets and the fused path bodies (dls_chain_path_body, hot_path_body).
+IKD_FN void line_start_from_pose(const double (&from)[12], const double (&goal)[12], LineStart &s) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s.R0[k] = from[k];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) s.p0[i] = from[9 + i];
+    double Rrel[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Rrel[3 * i + j] = dfma(s.R0[i], goal[j], dfma(s.R0[3 + i], goal[3 + j], s.R0[6 + i] * goal[6 + j]));
+    log3(Rrel, s.w);
+}
+
+// What the path kernels take after the solve's arguments (include/ikgpu.h ikgpu_dls_path_batch): P segments of T waypoints each.
+struct PathArgs {
+    int32_t *reached;        // [B] or null: waypoints met before the first one that was not (P * T: the whole path)
+    int T, P;                // waypoints per segment >= 1, segments >= 1
+    double max_joint_step;   // 0: no joint-step rule; else a waypoint is met only when no chain entry moved by more than this
+};
+
+// "Some entry of the support moved by more than max_step between the start of the solve and its result": one subtraction, fabs and a
+// compare per entry, on plain entries (no distance modulo 2 pi), as solutions_near (solutions.hpp).  max_step == 0: the rule is off.
+template <int NJ>
+IKD_FN bool path_jumped(const double (&q)[NJ], const double (&q_prev)[NJ], double max_step) {
+    bool jumped = false;
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) jumped = jumped || __builtin_fabs(q[i] - q_prev[i]) > max_step;
+    return jumped && max_step != 0.0;
 }
 
 // Waypoint k of T (0 <= k < T), s = (k + 1) / T: R = R0 exp3(s w), p = p0 + s (p1 - p0) -- a straight line of the frame origin at

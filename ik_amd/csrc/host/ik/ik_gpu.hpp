@@ -728,6 +728,32 @@ inline void dls_line_device(InverseKinematicsProblem &problem, std::int64_t B, s
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// A Cartesian path through P via poses per problem on DEVICE buffers: dls_track_device on the P T waypoints ikgpu_path_targets defines
+// (segment 0 from the pose at Q0 to via 0, segment s from via s - 1 to via s; the caller's target sequence as a formula,
+// ik_ros/src/cassie.cpp:92-113), a problem taking part in waypoint n only while its earlier waypoints were met: the solve met the stop rule
+// (ik/ik/dls.cpp:61-64,76-77) and, with max_joint_step > 0, no support entry moved by more than max_joint_step from the configuration the
+// solve started from.  vias [P][ntasks][12][B]; Q [P T][nq][B], success / iterations [P T][B] (may be null): slabs
+// n <= min(reached[b], P T - 1) are written; reached [B] (may be null) counts the waypoints met before the first that was not.
+// workspace: device memory of path_workspace_bytes() bytes (0 for a chain problem: one launch).  Asynchronous on `stream`.
+inline std::size_t path_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, std::int64_t P, std::int64_t T, dls_data &data,
+                                        const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                        const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_path_workspace_bytes(data.handle(), B, P, T, &prm);
+}
+inline void dls_path_device(InverseKinematicsProblem &problem, std::int64_t B, std::int64_t P, std::int64_t T, const number_t *Q0,
+                            const number_t *vias, number_t max_joint_step, dls_data &data, number_t *Q, std::uint8_t *success,
+                            std::int32_t *iterations, std::int32_t *reached, void *workspace, std::size_t workspace_bytes, void *stream,
+                            const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                            const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_path_batch(data.handle(), B, P, T, Q0, vias, &prm, max_joint_step, Q, success, iterations, reached, IKGPU_SOA, workspace,
+                             workspace_bytes, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // Any of G alternative goals per problem from K starts on DEVICE buffers (G x K <= 64): candidate g K + k is dls_batch_device from start k
 // (dls_multistart_device's starts) against slab g of goals [G][ntasks][12][B]; the winner is the first candidate that met the stop rule
 // -- the lowest goal, within it the lowest start -- else the one with the smallest squared weighted error, and Q / success / iterations

@@ -144,6 +144,104 @@ __global__ __launch_bounds__(256) void line_reached_kernel(int64_t B, int T, con
     reached[b] = n;
 }
 
+// A Cartesian path through P vias per problem with the joint-step rule in one launch (device/chain_kernel_body.hpp dls_chain_path_body):
+// the general build's path kernel.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_path_kernel(const ChainKernelArgs<NJ> a, const ikdev::PathArgs pa) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    (void)ikdev::dls_chain_path_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, pa, gid, ikdev::KeepGoing{0, 0, 0});
+}
+
+// The waypoints of ikgpu_path_targets for a chain problem: a.targets holds the P slabs of vias, a.oMf_out the P x T slabs.
+template <int NJ>
+__global__ __launch_bounds__(kBlock) void path_targets_chain_kernel(const ChainKernelArgs<NJ> a, const int P, const int T) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (b >= a.B) return;
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;
+    double q[NJ], via[12];
+    ikdev::line_load(a, b, q, via);
+    ikdev::LineStart ls;
+    ikdev::line_chain_start(a, *(ConstDesc *)a.desc, q, via, ls);
+    for (int s = 0; s < P; ++s) {
+        if (s > 0) {
+            double next[12];
+            ikdev::load_target_raw(a, a.targets + static_cast<int64_t>(s) * 12 * a.B, b, next);
+            ikdev::line_start_from_pose(via, next, ls);
+#pragma unroll
+            for (int c = 0; c < 12; ++c) via[c] = next[c];
+        }
+        for (int k = 0; k < T; ++k) {
+            double t[12];
+            ikdev::line_waypoint(ls, via, k, T, t);
+            double *out = a.oMf_out + (static_cast<int64_t>(s) * T + k) * 12 * a.B;
+#pragma unroll
+            for (int c = 0; c < 12; ++c) out[ikdev::at(a.layout, a.B, 12, c, b)] = t[c];
+        }
+    }
+}
+
+struct PathTargetsArgs {
+    const double *ref_pl, *vias;
+    double *out;
+    int64_t B;
+    int ntasks, P, T, layout;
+};
+__global__ __launch_bounds__(256) void path_targets_from_fk_kernel(const PathTargetsArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= a.B * a.ntasks) return;
+    const int64_t b = i % a.B;
+    const int s = static_cast<int>(i / a.B);
+    const int64_t slab = static_cast<int64_t>(a.ntasks) * 12 * a.B;
+    double f[12], via[12], ref[12];
+#pragma unroll
+    for (int c = 0; c < 12; ++c) {
+        const int64_t at = ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b);
+        f[c] = a.out[at];   // slab 0: oMf(q0) of this slot, read before waypoint 0 goes over it
+        via[c] = a.vias[at];
+        ref[c] = a.ref_pl[s * 12 + c];
+    }
+    const double Rf[9] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]}, pf[3] = {f[9], f[10], f[11]};
+    ikdev::LineStart ls;
+    ikdev::line_start(ref, Rf, pf, via, ls);
+    for (int seg = 0; seg < a.P; ++seg) {
+        if (seg > 0) {
+            double next[12];
+#pragma unroll
+            for (int c = 0; c < 12; ++c) next[c] = a.vias[seg * slab + ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b)];
+            ikdev::line_start_from_pose(via, next, ls);
+#pragma unroll
+            for (int c = 0; c < 12; ++c) via[c] = next[c];
+        }
+        for (int k = 0; k < a.T; ++k) {
+            double t[12];
+            ikdev::line_waypoint(ls, via, k, a.T, t);
+            double *out = a.out + (static_cast<int64_t>(seg) * a.T + k) * slab;
+#pragma unroll
+            for (int c = 0; c < 12; ++c) out[ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b)] = t[c];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void path_reached_kernel(const PathReached r) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= r.B) return;
+    const int64_t q_slab = static_cast<int64_t>(r.nq) * r.B;
+    int n = 0;
+    for (; n < r.N && r.success[n * r.B + b]; ++n) {
+        if (r.max_joint_step == 0.0) continue;
+        const double *prev = n == 0 ? r.q0 : r.q_traj + (n - 1) * q_slab, *cur = r.q_traj + n * q_slab;
+        bool jumped = false;
+        for (int i = 0; i < r.nq; ++i) {
+            if (!r.support[i]) continue;
+            const int64_t at = ikdev::at(r.layout, r.B, r.nq, i, b);
+            jumped = jumped || __builtin_fabs(cur[at] - prev[at]) > r.max_joint_step;
+        }
+        if (jumped) break;
+    }
+    r.reached[b] = n;
+}
+
 // K starts per problem in one launch, the best one stored (device/chain_kernel_body.hpp dls_chain_multistart_body): the general build's
 // multi-start kernel.
 template <int NJ, int KT, int SMASK>
@@ -332,8 +430,9 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         constexpr int SM = decltype(smask)::value;
         if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
         const dim3 grid = grid_for(job.lanes(io.B));
-        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line) && prm.stop_sq_tol < 0.0) return hipErrorInvalidValue;
-        if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
+        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line || job.kind == ChainJob::Path) && prm.stop_sq_tol < 0.0) return hipErrorInvalidValue;
+        if (job.kind == ChainJob::Path) hipLaunchKernelGGL((dls_chain_path_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.path);
+        else if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
         else if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
         else if (job.kind == ChainJob::Solutions) hipLaunchKernelGGL((dls_chain_solutions_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.sol);
         else if (job.kind == ChainJob::Goalset) hipLaunchKernelGGL((dls_chain_goalset_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.goal);
@@ -532,6 +631,34 @@ hipError_t launch_line_targets_from_fk(int64_t B, int ntasks, int T, const doubl
 
 hipError_t launch_line_reached(int64_t B, int T, const uint8_t *success, int32_t *reached, hipStream_t stream) {
     hipLaunchKernelGGL(line_reached_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, T, success, reached);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_targets_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, int P, int T, const double *q0, const double *vias,
+                                     double *out, int layout, hipStream_t stream) {
+    const int nj = ph.chain.nj;
+#define X(N)                                                                                                 \
+    if (nj == N) {                                                                                           \
+        ChainKernelArgs<N> a = make_args<N>(ph, dt);                                                         \
+        a.layout = layout; a.B = B; a.q0 = q0; a.targets = vias; a.oMf_out = out;                            \
+        hipLaunchKernelGGL((path_targets_chain_kernel<N>), grid_for(B), dim3(kBlock), 0, stream, a, P, T);   \
+        return hipGetLastError();                                                                            \
+    }
+    IKGPU_FOR_NJ(X)
+#undef X
+    not_built(nj, 0);
+}
+
+hipError_t launch_path_targets_from_fk(int64_t B, int ntasks, int P, int T, const double *ref_pl, const double *vias, double *out, int layout,
+                                       hipStream_t stream) {
+    const PathTargetsArgs a{ref_pl, vias, out, B, ntasks, P, T, layout};
+    const int64_t n = B * ntasks;
+    hipLaunchKernelGGL(path_targets_from_fk_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_reached(const PathReached &r, hipStream_t stream) {
+    hipLaunchKernelGGL(path_reached_kernel, dim3(static_cast<unsigned>((r.B + 255) / 256)), dim3(256), 0, stream, r);
     return hipGetLastError();
 }
 

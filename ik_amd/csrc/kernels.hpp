@@ -86,15 +86,20 @@ struct BatchIO {
 //   Goalset:    G x K = 1 << (goal.log2G + goal.ms.log2K) candidates per problem in ONE launch, start k against goal g, the best one stored
 //               and each goal's reachability (ikgpu_dls_goalset_batch; dls_chain_goalset_body, hot_goalset_body): `io.targets` holds the G
 //               slabs of goals, B x G x K lanes.
-// Track, Multistart, Solutions, Line and Goalset are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
+//   Path:       P x T chained solves per problem in ONE launch along the Cartesian path through the problem's P via poses, with the
+//               joint-step rule (ikgpu_dls_path_batch; dls_chain_path_body, hot_path_body): `io.targets` holds the P slabs of vias, the
+//               waypoints are formed on the lane (device/line.hpp), a problem stops at its first waypoint that was not met and
+//               path.reached counts the ones before it.  Needs a stop rule, as Line.
+// Track, Multistart, Solutions, Line, Goalset and Path are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
 // capturable.
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset } kind = Solve;
+    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset, Path } kind = Solve;
     int T = 0;                     // Track: the number of waypoints
     ikdev::MultistartArgs ms{};    // Multistart
     ikdev::SolutionsArgs sol{};    // Solutions
     ikdev::LineArgs line{};        // Line
     ikdev::GoalsetArgs goal{};     // Goalset
+    ikdev::PathArgs path{};        // Path
     int64_t lanes(int64_t B) const {   // one lane per problem, per start, or per (goal, start)
         return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : B;
     }
@@ -117,6 +122,25 @@ hipError_t launch_line_targets_from_fk(int64_t B, int ntasks, int T, const doubl
                                        hipStream_t stream);
 // reached[b] = the number of leading ones in success[0 .. T-1][b] (ikgpu_dls_line_batch run as the loop over the single solve).
 hipError_t launch_line_reached(int64_t B, int T, const uint8_t *success, int32_t *reached, hipStream_t stream);
+// The P x T waypoints of ikgpu_path_targets (device/line.hpp) into `out` [P T][ntasks x 12 x B]; `vias` is [P][ntasks x 12 x B].  A chain
+// problem: FK at q0 and every segment's waypoints in one kernel, on the arithmetic the fused path kernels use.
+hipError_t launch_path_targets_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, int P, int T, const double *q0, const double *vias,
+                                     double *out, int layout, hipStream_t stream);
+// Every other kind: as launch_line_targets_from_fk -- `out`'s slab 0 holds oMf(q0) of every target slot, read before it is written.
+hipError_t launch_path_targets_from_fk(int64_t B, int ntasks, int P, int T, const double *ref_pl, const double *vias, double *out, int layout,
+                                       hipStream_t stream);
+// The met rule of ikgpu_dls_path_batch run as the loop over the single solve: reached[b] = the number of leading waypoints n < N with
+// success[n][b] set and, when max_joint_step > 0, no support entry i (support [nq], DeviceTables::q_in_chain) with
+// fabs(q_traj[n][i] - q_prev[i]) > max_joint_step, q_prev = q0 for n = 0 and slab n - 1 after that.
+struct PathReached {
+    int64_t B;
+    int nq, N, layout;
+    double max_joint_step;
+    const uint8_t *support, *success;   // [nq], [N][B]
+    const double *q0, *q_traj;          // [nq x B], [N][nq x B]
+    int32_t *reached;                   // [B]
+};
+hipError_t launch_path_reached(const PathReached &r, hipStream_t stream);
 // Starts k0 .. k1-1 (1 <= k0 <= k1) of every problem as ikgpu_multistart_starts defines them, start k into slab k - k0 of `out`.
 hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,
                                     int layout, hipStream_t stream);

@@ -77,6 +77,13 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_line_kernel(const ChainK
     ikdev::hot_line_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, la);
 }
 
+// A Cartesian path through P vias per problem with the joint-step rule in one launch (device/chain_hot.hpp hot_path_body; include/ikgpu.h
+// ikgpu_dls_path_batch).  Stop rule only; lock-step per waypoint; no LDS, no queue slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_path_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::PathArgs pa) {
+    ikdev::hot_path_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pa);
+}
+
 // X(NJ, code0, code1, code2)
 #define IKGPU_HOT_SHAPES(X)                                                                                                   \
     X(7, 0x04f0208cce8c7664ull, 0x395959cacad65656ull, 0x000001cacace5656ull) /* Cassie leg: Left / RightFootFront, 22 values */ \
@@ -140,6 +147,9 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
         } else if (job.kind == ChainJob::Line) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (nothing is ever reached without a stop rule: refused likewise)
             else hipLaunchKernelGGL((dls_chain_hot_line_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.line);
+        } else if (job.kind == ChainJob::Path) {
+            if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
+            else hipLaunchKernelGGL((dls_chain_hot_path_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.path);
         } else if constexpr (NEVER) {
             hipLaunchKernelGGL((dls_chain_hot_kernel<NJ, C0, C1, C2, true>), grid, block, 0, stream, a, t);
         } else {

@@ -129,7 +129,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 //       ikdev::<entry><NJ, S<flag>>(a, t<args>);
 //   }
 enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotSolutionsStop, kHotLineStop,
-       kHotGoalsetNever, kHotGoalsetStop, kHotEntries };
+       kHotGoalsetNever, kHotGoalsetStop, kHotPathStop, kHotEntries };
 struct HotEntry {
     const char *name, *params, *entry, *flag, *args;
     bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
@@ -151,11 +151,14 @@ const HotEntry kHotEntryTable[kHotEntries] = {
     // G goals and K starts per problem in one launch, the best candidate stored (ikgpu_dls_goalset_batch)
     {"ikgpu_hot_goalset_never", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", true", ", ga", false},
     {"ikgpu_hot_goalset_stop", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", false", ", ga", false},
+    // a Cartesian path through P vias per problem with the joint-step rule (ikgpu_dls_path_batch): a stop rule always, so one entry
+    {"ikgpu_hot_path_stop", ", const ikdev::PathArgs pa", "hot_path_entry", "", ", pa", false},
 };
-// The row of a job, or -1: a solution-set or line job has no never-stop entry.
+// The row of a job, or -1: a solution-set, line or path job has no never-stop entry.
 int hot_entry(ChainJob::Kind kind, bool never) {
     if (kind == ChainJob::Solutions) return never ? -1 : kHotSolutionsStop;
     if (kind == ChainJob::Line) return never ? -1 : kHotLineStop;
+    if (kind == ChainJob::Path) return never ? -1 : kHotPathStop;
     if (kind == ChainJob::Goalset) return never ? kHotGoalsetNever : kHotGoalsetStop;
     static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
     return first[kind] + (never ? 0 : 1);
@@ -562,15 +565,18 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
             ikdev::SolutionsArgs sa;
             ikdev::LineArgs la;
             ikdev::GoalsetArgs ga;
+            ikdev::PathArgs pa;
         } tail;
     } args{};
     constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
     static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8 &&
-                      alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8 && alignof(ikdev::GoalsetArgs) == 8, "argument layout");
+                      alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8 && alignof(ikdev::GoalsetArgs) == 8 &&
+                      alignof(ikdev::PathArgs) == 8, "argument layout");
     constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
                      kBytesTrack = offsetof(Args, tail.T) + sizeof(int),
                      kBytesMultistart = offsetof(Args, tail) + sizeof(ikdev::MultistartArgs), kBytesSolutions = offsetof(Args, tail) + sizeof(ikdev::SolutionsArgs),
-                     kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs), kBytesGoalset = offsetof(Args, tail) + sizeof(ikdev::GoalsetArgs);
+                     kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs), kBytesGoalset = offsetof(Args, tail) + sizeof(ikdev::GoalsetArgs),
+                     kBytesPath = offsetof(Args, tail) + sizeof(ikdev::PathArgs);
     static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
     static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
     static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
@@ -578,6 +584,7 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     static_assert(kBytesSolutions == kHead + sizeof(ikdev::SolutionsArgs), "solution set: the whole of (a, t, sa)");
     static_assert(kBytesLine == kHead + sizeof(ikdev::LineArgs), "line: the whole of (a, t, la)");
     static_assert(kBytesGoalset == kHead + sizeof(ikdev::GoalsetArgs), "goal set: the whole of (a, t, ga)");
+    static_assert(kBytesPath == kHead + sizeof(ikdev::PathArgs), "path: the whole of (a, t, pa)");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
     fill_chain_kernel_args(a, ph, dt);
     fill_solve_args(a, io, prm);
@@ -599,6 +606,10 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     if (job.kind == ChainJob::Line) {
         args.tail.la = job.line;
         return launch(entry, waves, kBytesLine);
+    }
+    if (job.kind == ChainJob::Path) {
+        args.tail.pa = job.path;
+        return launch(entry, waves, kBytesPath);
     }
     if (job.kind == ChainJob::Goalset) {
         args.tail.ga = job.goal;

@@ -360,6 +360,50 @@ size_t ikgpu_dls_line_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t
  * waypoint.  The string belongs to the calling thread and lasts until its next call. */
 const char *ikgpu_dls_line_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
 
+/* ---- path: a Cartesian path through P via poses per problem -- approach, grasp, retreat; a foot's lift, swing and touch-down -- with T
+ * waypoints per segment and a bound on the joint step between waypoints.  The sequence is still the caller's formula
+ * (ik_ros/src/cassie.cpp:92-113); here it is a polyline.  ikgpu_path_targets writes the P * T waypoints, W_out [P*T][ntasks x 12 x B], from
+ *   vias [P][ntasks x 12 x B]  P slabs, each with the shape, the meaning and the batch layout of ikgpu_dls_solve_batch's targets;
+ *   segment 0 runs from M0 = oMr^-1 oMf(q0), the pose of each task frame at q0 in its reference frame, to via 0: exactly
+ *   ikgpu_line_targets(q0, via 0);
+ *   segment s >= 1 runs from via s-1's own twelve values (R0, p0) to via s, w = log3(R0^T R1);
+ *   waypoint n = s*T + k is the line's waypoint k of T of segment s (R = R0 exp3((k+1)/T w), p = p0 + (k+1)/T (p1 - p0)), and waypoint
+ *   s*T + T-1 is via s's own 12 doubles, bit for bit.
+ * The slot restrictions, log3 / exp3 and the advice on rotations near pi are ikgpu_line_targets'.  P >= 1, T >= 0, P * T <= 0x7fffffff,
+ * else IKGPU_ERR_INVALID; B == 0 or T == 0 is a no-op.  W_out must not overlap q0 or vias.  DEVICE pointers; asynchronous on `stream`. */
+int ikgpu_path_targets(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const double *q0, const double *vias,
+                       double *W_out /* [P*T][ntasks x 12 x B] */, int layout /* ikgpu_layout */, void *stream);
+/* ikgpu_dls_path_batch is DEFINED as ikgpu_dls_track_batch on W = ikgpu_path_targets(q0, vias), with problem b taking part in waypoint n
+ * only while all its earlier waypoints were MET.  Waypoint n is met when its solve met the stop rule (the reference's own stop test and
+ * failure report, ik/ik/dls.cpp:61-64,76-77) and either max_joint_step == 0 or no entry i with ikgpu_problem_support = 1 has
+ *   fabs(q_n[i] - q_prev[i]) > max_joint_step,
+ * q_prev being the configuration the solve started from: q0 for n = 0, slab n-1 of q_traj after that (one IEEE subtraction, fabs and a
+ * compare on plain entries, as the solution set compares them: no distance modulo 2 pi).  The stop rule alone says nothing about the
+ * joints: with 100 iterations per waypoint a solve may reach waypoint n from waypoint n-1's configuration by swinging to another branch,
+ * and a "straight-line motion" would contain a joint-space jump (the joint-jump threshold of every Cartesian-path interface).
+ *   reached [B] (int32, may be NULL)  the waypoints met before the first one that was not; P * T: the whole path
+ *   q_traj [P*T][nq x B], success [P*T][B] (may be NULL), iters [P*T][B] (may be NULL): slabs n <= min(reached[b], P*T-1) of problem b
+ *   are written and are bit-identical to ikgpu_dls_track_batch on W; later slabs of that problem are unspecified.  The failing slab
+ *   carries the solve's own success: 1 there means the waypoint was reached, but through a jump.
+ * max_joint_step must be finite and >= 0 and, under the never-stop visitor (stop_sq_tol < 0 and no derived visitor), nothing is ever
+ * reached: IKGPU_ERR_INVALID.  P = 1 with max_joint_step = 0 is ikgpu_dls_line_batch.  A chain problem under the reference's visitor runs
+ * ONE launch (`dls_chain_path<...>`): a lane loads q0 and P x 12 doubles (not P * T x 12), keeps q, the previous configuration's chain
+ * entries, the segment's start pose and rotation vector and the current via in registers, and has the next via in flight during the
+ * last solve of a segment; a lane whose path has ended is inactive from then on and the wave leaves once none of its lanes is alive (no
+ * queue slot, no allocation: capturable in a graph; `workspace` is not read).  Every other problem kind and the derived visitors run
+ * the definition from inside the call -- ikgpu_path_targets into `workspace` (DEVICE memory of at least
+ * ikgpu_dls_path_workspace_bytes bytes, else IKGPU_ERR_INVALID), the P * T launches, and one kernel that applies the met rule to the
+ * flags and the joint steps (the flags live in the workspace when success is NULL). */
+int ikgpu_dls_path_batch(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const double *q0, const double *vias,
+                         const ikgpu_dls_params *params, double max_joint_step, double *q_traj, uint8_t *success, int32_t *iters,
+                         int32_t *reached, int layout /* ikgpu_layout */, void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of `workspace` ikgpu_dls_path_batch needs for these arguments: 0 for the single launch. */
+size_t ikgpu_dls_path_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const ikgpu_dls_params *params);
+/* Name of what ikgpu_dls_path_batch runs with these parameters: `dls_chain_path<NJ=7,full,hot>` (or hot-rtc / general: the build
+ * ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the definition run waypoint after
+ * waypoint.  The string belongs to the calling thread and lasts until its next call. */
+const char *ikgpu_dls_path_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
+
 /* ---- goal set: reach ANY of G alternative goal poses per problem -- G grasp candidates on an object, G footholds, G docking poses --
  * from K starts, and learn which goals are reachable at all.  ik::dls is a local method (reference ik/ik/dls.cpp:10 "todo - if limited
  * convergence, try random walk"; dls.cpp:73 "If issues, perform random restart"; dls_parameters::random_restart, ik/ik/dls.hpp:27, is a
