@@ -118,6 +118,91 @@ struct HotTable {
     double v[kHotTableMax];
 };
 
+// ---- the table of dsincos_lut (lane_math.hpp) as the lane programs reach it: through their Tab argument --------------------------
+// A plain HotTable (the host emulators and shims under tests/) reads the header's array where it stands.  The kernels pass a
+// HotTableLds, which carries a pointer to the workgroup's copy in LDS beside v[]: one ds_read_b128 per angle, on the one pipe these
+// kernels otherwise leave idle.  Both read the same 2048 doubles, so every job and both stop-rule modes compute the same bits.
+// DEVICE code that hands the lane program a plain HotTable does not compile (the overload is deleted there): an entry that forgets
+// IKD_HOT_LUT_DECLARE must not fall back to reading the table from HBM unnoticed.  The phase probes of tools/, which wrap single
+// functions in kernels of their own, ask for that path by name: IKD_HOT_LUT_FROM_HBM, defined ahead of this header.
+struct HotLutNoStage {};
+#if IKD_HIP_LANG
+typedef double SinCosPair __attribute__((ext_vector_type(2)));   // {sin, cos}, 16 bytes
+// the header's literals, device-resident, once per translation unit: what the entries stage into LDS (mathematical constants, the
+// same on every call)
+static __device__ const double kSinCosLutDevice[2 * IKD_SINCOS_LUT_SIZE] __attribute__((aligned(16), unused)) = {IKD_SINCOS_LUT_VALUES};
+struct HotTableLds : HotTable {
+    SinCosPair *lut;   // IKD_SINCOS_LUT_SIZE entries of static __shared__ memory (IKD_HOT_LUT_DECLARE), filled by hot_lut_commit
+};
+constexpr int kHotLutPerLane = IKD_SINCOS_LUT_SIZE / 64;   // one wave64 per workgroup: 16 entries of 16 bytes per lane
+struct HotLutStage { SinCosPair v[kHotLutPerLane]; };
+// The fill in two halves, so that a body can put its own loads from HBM between them: hot_lut_issue starts the 16 loads of this lane
+// (entries lane + 64 i: consecutive lanes read consecutive 16 bytes), hot_lut_commit writes them to LDS.  A body calls the first ahead
+// of its q0 and target loads and the second behind them -- one round trip to HBM for all of it -- and in front of its pass-through
+// stores.  One wave per workgroup: LDS serves a wave's accesses in order, so the reads that follow see the writes of every lane
+// without a barrier; the fence keeps the compiler from moving a read above them.
+__device__ __forceinline__ HotLutStage hot_lut_issue(const HotTableLds &) {
+    HotLutStage st;
+    const SinCosPair *src = reinterpret_cast<const SinCosPair *>(kSinCosLutDevice);
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+#pragma unroll
+    for (int i = 0; i < kHotLutPerLane; ++i) st.v[i] = src[lane + 64 * i];
+    return st;
+}
+__device__ __forceinline__ void hot_lut_commit(const HotTableLds &t, const HotLutStage &st) {
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+#pragma unroll
+    for (int i = 0; i < kHotLutPerLane; ++i) t.lut[lane + 64 * i] = st.v[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+__device__ __forceinline__ void hot_lut_fetch(const HotTableLds &t, int idx, double &S, double &C) {
+    const SinCosPair e = t.lut[idx];
+    S = e.x;
+    C = e.y;
+}
+// in a kernel entry: the 16 KB table and the table object `tv` that carries it
+#define IKD_HOT_LUT_DECLARE(tv)                                       \
+    __shared__ SinCosPair ikd_hot_lut[IKD_SINCOS_LUT_SIZE];           \
+    HotTableLds tv;                                                   \
+    tv.lut = ikd_hot_lut
+#endif
+IKD_FN HotLutNoStage hot_lut_issue(const HotTable &) { return HotLutNoStage{}; }
+IKD_FN void hot_lut_commit(const HotTable &, const HotLutNoStage &) {}
+#if IKD_ON_DEVICE && !defined(IKD_HOT_LUT_FROM_HBM)
+void hot_lut_fetch(const HotTable &, int idx, double &S, double &C) = delete;
+#else
+IKD_FN void hot_lut_fetch(const HotTable &, int idx, double &S, double &C) {
+#if IKD_ON_DEVICE
+    S = kSinCosLutDevice[2 * idx];
+    C = kSinCosLutDevice[2 * idx + 1];
+#else
+    S = kSinCosLutHost[2 * idx];
+    C = kSinCosLutHost[2 * idx + 1];
+#endif
+}
+#endif
+
+// sin and cos of NJ angles at once, the form the hot loops run (hot_evaluate; tools/hot_phase_count.hip counts this very function):
+// dsincos_lut in its pieces, ordered by hand because a lone wave hides the table read behind nothing else -- every reduction and
+// index, then the NJ reads in the order the tip-to-base walk consumes them, then the residual polynomials, which need nothing from
+// the table, then the combinations.
+template <int NJ, class Tab>
+IKD_FN void hot_sincos(const Tab &t, const double (&phi)[NJ], double (&sn)[NJ], double (&cs)[NJ]) {
+    double res[NJ], tS[NJ], tC[NJ], sl[NJ], cm1[NJ];
+    int idx[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) dsincos_lut_reduce(phi[j], res[j], idx[j]);
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) hot_lut_fetch(t, idx[j], tS[j], tC[j]);
+    IKD_SCHED_FENCE();   // (left alone the scheduler issues the reads behind the polynomials and waits for them at once)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) dsincos_lut_poly(res[j], sl[j], cm1[j]);
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) dsincos_lut_combine(tS[j], tC[j], sl[j], cm1[j], sn[j], cs[j]);
+}
+
 // entry e = 3 m + k of placement I's rotation: the literal 0.0 / +-1.0 when structural, else its table value
 template <class S, int I, class Tab>
 IKD_FN double hot_rot(const Tab &t, int e) {
@@ -187,7 +272,7 @@ IKD_FN void hot_fold_base(const Tab &t, const double (&oMt)[12], double (&oM0)[1
 //    addition along the axis; a member without in-plane translation needs no sin / cos at all;
 //  * A lin_j = p~0 (A r1) - p~1 (A r0): the two products are formed once per run and lin_j itself never;
 //  * at the leader (R, p) <- P_L Rz(phi_L) (R, p~): the same rot_z_left and hot_compose_left as for a lone joint.
-// The step, the joint limits and q stay per joint (hot_step); only sin and cos take phi_j.  Argument of dsincos_hot: its one-word
+// The step, the joint limits and q stay per joint (hot_step); only sin and cos take phi_j.  Argument of dsincos_lut: its one-word
 // reduction by 2 pi leaves an error of 3.9e-17 |x|.  Every joint of a chain problem is a bounded revolute (continuous joints go to
 // the generic kernel) and q is clipped to its limits after every step, so from the second evaluation on |phi_j| <= the sum of the
 // run's max(|lo|, |hi|).  Nothing bounds a URDF's limits (or the caller's q0, which the first evaluation sees unclipped), so this is
@@ -196,17 +281,17 @@ IKD_FN void hot_fold_base(const Tab &t, const double (&oMt)[12], double (&oM0)[1
 // give |phi| = 700 and 2.7e-14.  The folded form's error thus grows with the run's SUM where the unfolded one grew with each joint's own
 // angle.  The second word of 2 pi (dsincos_fast) would not change that: phi_j is a rounded sum, each of its additions is off by up to
 // half an ulp of |phi| (5.5e-17 .. 1.1e-16 |phi|), more than the dropped word's 3.9e-17 |phi|.  So the one-word reduction stays.
+// (The bounds above were written for dsincos_hot's 2e-15; dsincos_lut has the same reduction and 3.4e-16 of its own, lane_math.hpp.)
 // BASE_FOLDED: oMt is hot_fold_base's P_0^-1 oMt and joint 0 -- alone or as the leader of a folded run -- ends the walk with its own
 // rotation, no hot_compose_left<S, 0>.  The columns are read off Y before that composition either way: the same expressions.
 template <int NJ, class S, bool BASE_FOLDED = false, class Tab>
 IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt)[12], double (&e)[6], double (&col)[NJ][6]) {
     constexpr typename ChainRuns<S, NJ>::Table kRuns = ChainRuns<S, NJ>::value;
-    // the NJ sin / cos first: independent of the chain, the constants are live once.  A member of a folded run takes phi_j.
+    // the NJ sin / cos first: independent of the chain.  A member of a folded run takes phi_j.
     double phi[NJ], sn[NJ], cs[NJ];
 #pragma unroll
     for (int j = NJ - 1; j >= 0; --j) phi[j] = (kRuns.folded[j] && !kRuns.tip[j]) ? phi[j + 1 < NJ ? j + 1 : j] + q[j] : q[j];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) dsincos_hot(phi[j], sn[j], cs[j]);
+    hot_sincos<NJ>(t, phi, sn, cs);
 
     double ang[NJ][3], lin[NJ][3];
     double rows[NJ][6], pt[NJ][2];   // folded runs: rows 0 and 1 of R at the run's entry (by leader), p~0 and p~1 (by member)
@@ -467,6 +552,15 @@ IKD_FN void hot_pass_through(const ChainKernelArgs<NJ> &a, int64_t b, bool stepp
 // The hot program under lane refill (chain_kernel_body.hpp chain_refill_loop): the stop-rule mode for batches larger than the machine.
 template <int NJ, class S, class Tab>
 __device__ __forceinline__ void hot_refill_body(const ChainKernelArgs<NJ> &a, const Tab &t, unsigned long long *queue, int chunk) {
+    // The sin / cos table is filled by the loop's stage hook: only by a wave that has work (with every problem stopped in the first
+    // phase the whole grid leaves at once, and a fill there would be the launch's entire cost), its loads in flight beside the first
+    // round's q and target loads as in hot_chain_body.
+    struct Stage {
+        const Tab &t;
+        decltype(hot_lut_issue(t)) st;
+        __device__ __forceinline__ void issue() { st = hot_lut_issue(t); }
+        __device__ __forceinline__ void commit() { hot_lut_commit(t, st); }
+    };
     // (the loop's oMt holds P_0^-1 oMt: folded by the hook below where a lane takes a target, as hot_dls folds at entry -- the same bits)
     chain_refill_loop<NJ>(a, queue, chunk, [&](double (&q)[NJ], const double (&oMt)[12], bool have) {
         constexpr int M = 6;
@@ -489,7 +583,7 @@ __device__ __forceinline__ void hot_refill_body(const ChainKernelArgs<NJ> &a, co
 #pragma unroll
         for (int k = 0; k < 12; ++k) w[k] = oMt[k];
         hot_fold_base<S>(t, w, oMt);
-    });
+    }, Stage{t, {}});
 }
 #endif
 
@@ -503,11 +597,13 @@ IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t g
 #endif
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
+    const auto lut_stage = hot_lut_issue(t);   // the sin / cos table's loads travel with the ones of q0 and the target (hot_lut_issue)
     double q[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
     double oMt[12];
     load_target(a, b, oMt);
+    hot_lut_commit(t, lut_stage);
     // The visitor never stops: every lane takes max_iterations steps, so what happens to the entries outside the support is
     // known before the loop -- copy them now (the stores drain while the loop runs) instead of after it (4 us of epilogue).
     if (NEVERSTOP && valid) hot_pass_through(a, b, a.prm.max_iterations > 0);
@@ -556,6 +652,7 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
     const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
     double q[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
@@ -568,6 +665,7 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
         compose_target(a, next, oMt);
     }
     if (T > 1) load_target_raw(a, a.targets + t_slab, b, next);
+    hot_lut_commit(t, lut_stage);
     bool stepped = NEVERSTOP && a.prm.max_iterations > 0;   // (never-stop: every waypoint takes max_iterations steps, known here)
     for (int k = 0; k < T; ++k) {
         double *q_out = a.q_out + k * q_slab;
@@ -598,8 +696,10 @@ IKD_FN int hot_line_body(const ChainKernelArgs<NJ> &a, const Tab &t, const LineA
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
     const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B;
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
     double q[NJ], goal[12];
     line_load(a, b, q, goal);
+    hot_lut_commit(t, lut_stage);
     LineStart ls;
     typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
     line_chain_start(a, *(ConstDesc *)a.desc, q, goal, ls);
@@ -638,8 +738,10 @@ IKD_FN int hot_path_body(const ChainKernelArgs<NJ> &a, const Tab &t, const PathA
     const bool valid = gid < a.B;
     const int64_t b = valid ? gid : a.B - 1;  // tail lanes shadow the last problem and store nothing
     const int64_t q_slab = static_cast<int64_t>(a.nq) * a.B, t_slab = 12 * a.B;
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
     double q[NJ], q_prev[NJ], via[12], next[12];
     line_load(a, b, q, via);
+    hot_lut_commit(t, lut_stage);
     LineStart ls;
     typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
     line_chain_start(a, *(ConstDesc *)a.desc, q, via, ls);
@@ -686,9 +788,11 @@ IKD_FN int hot_path_body(const ChainKernelArgs<NJ> &a, const Tab &t, const PathA
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
 IKD_FN void hot_multistart_lane(const ChainKernelArgs<NJ> &a, const MultistartArgs &ms, const Tab &t, int64_t b, int k, double (&q)[NJ],
                                 bool &success, int &iters, double &err_sq, AnyFn any_active) {
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
     multistart_load(a, ms, b, k, q);
     double oMt[12];
     load_target(a, b, oMt);
+    hot_lut_commit(t, lut_stage);
     hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);
     double e[6], col[NJ][6], oM0[12];
     hot_fold_base<S>(t, oMt, oM0);   // (hot_dls's own fold again: the same values, and P_0 stays out of the loop's live registers)
@@ -720,10 +824,12 @@ IKD_FN void hot_multistart_body(const ChainKernelArgs<NJ> &a, const MultistartAr
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
 IKD_FN void hot_goalset_lane(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga, const Tab &t, int64_t b, int g, int k, double (&q)[NJ],
                              bool &success, int &iters, double &err_sq, AnyFn any_active) {
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
     multistart_load(a, ga.ms, b, k, q);
     double raw[12], oMt[12];
     load_target_raw(a, a.targets + static_cast<int64_t>(g) * 12 * a.B, b, raw);
     compose_target(a, raw, oMt);
+    hot_lut_commit(t, lut_stage);
     hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);
     double e[6], col[NJ][6], oM0[12];
     hot_fold_base<S>(t, oMt, oM0);   // (hot_dls's own fold again: the same values, and P_0 stays out of the loop's live registers)
@@ -760,9 +866,11 @@ IKD_FN void hot_goalset_body(const ChainKernelArgs<NJ> &a, const GoalsetArgs &ga
 template <int NJ, class S, class Tab, class AnyFn>
 IKD_FN void hot_solutions_lane(const ChainKernelArgs<NJ> &a, const SolutionsArgs &sa, const Tab &t, int64_t b, int k, double (&q)[NJ],
                                bool &success, int &iters, AnyFn any_active) {
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
     multistart_load(a, sa.ms, b, k, q);
     double oMt[12];
     load_target(a, b, oMt);
+    hot_lut_commit(t, lut_stage);
     hot_dls<NJ, S, false>(t, a.prm, q, oMt, iters, success, any_active);
 }
 
@@ -823,7 +931,7 @@ __device__ __forceinline__ void hot_kernel_entry(const ChainKernelArgs<NJ> &a, c
     const unsigned block = blockIdx.x;
 #endif
     const int64_t gid = static_cast<int64_t>(block) * 64 + threadIdx.x;   // one wave64 per workgroup
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_chain_body<NJ, S, NEVERSTOP>(a, tv, gid, KeepGoing{a.leave_active, a.leave_after, 0}, wave_start);
 }
@@ -831,7 +939,7 @@ __device__ __forceinline__ void hot_kernel_entry(const ChainKernelArgs<NJ> &a, c
 template <int NJ, class S, bool NEVERSTOP>
 __device__ __forceinline__ void hot_track_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, int T) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_track_body<NJ, S, NEVERSTOP>(a, tv, T, gid, KeepGoing{0, 0, 0});
 }
@@ -839,7 +947,7 @@ __device__ __forceinline__ void hot_track_entry(const ChainKernelArgs<NJ> &a, co
 template <int NJ, class S>
 __device__ __forceinline__ void hot_line_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const LineArgs &la) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     (void)hot_line_body<NJ, S>(a, tv, la, gid, KeepGoing{0, 0, 0});
 }
@@ -847,7 +955,7 @@ __device__ __forceinline__ void hot_line_entry(const ChainKernelArgs<NJ> &a, con
 template <int NJ, class S>
 __device__ __forceinline__ void hot_path_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const PathArgs &pa) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     (void)hot_path_body<NJ, S>(a, tv, pa, gid, KeepGoing{0, 0, 0});
 }
@@ -855,7 +963,7 @@ __device__ __forceinline__ void hot_path_entry(const ChainKernelArgs<NJ> &a, con
 template <int NJ, class S, bool NEVERSTOP>
 __device__ __forceinline__ void hot_multistart_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const MultistartArgs &ms) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_multistart_body<NJ, S, NEVERSTOP>(a, ms, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
 }
@@ -863,7 +971,7 @@ __device__ __forceinline__ void hot_multistart_entry(const ChainKernelArgs<NJ> &
 template <int NJ, class S, bool NEVERSTOP>
 __device__ __forceinline__ void hot_goalset_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const GoalsetArgs &ga) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / (G x K) whole problems
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_goalset_body<NJ, S, NEVERSTOP>(a, ga, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{}, GoalsetBallot{});
 }
@@ -871,7 +979,7 @@ __device__ __forceinline__ void hot_goalset_entry(const ChainKernelArgs<NJ> &a, 
 template <int NJ, class S>
 __device__ __forceinline__ void hot_solutions_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const SolutionsArgs &sa) {
     const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     const int lane = static_cast<int>(threadIdx.x) & 63;
     hot_solutions_body<NJ, S>(a, sa, tv, gid, KeepGoing{0, 0, 0}, SolutionsShuffle{lane & ~((1 << sa.ms.log2K) - 1)});
@@ -879,7 +987,7 @@ __device__ __forceinline__ void hot_solutions_entry(const ChainKernelArgs<NJ> &a
 
 template <int NJ, class S>
 __device__ __forceinline__ void hot_refill_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, unsigned long long *queue, int chunk) {
-    HotTable tv;
+    IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_refill_body<NJ, S>(a, tv, queue, chunk);
 }

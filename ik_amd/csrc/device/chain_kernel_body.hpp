@@ -565,12 +565,19 @@ IKD_FN void dls_chain_solutions_body(const ChainKernelArgs<NJ> &a, const Solutio
 // iterate(q, oMt, have) runs ONE iteration of this lane's problem in place and returns "the visitor stopped it before the step".
 // on_target(oMt) is called once where a lane takes a target -- the first round and every refill --, in place: the hot program carries the
 // target into joint 0's frame there (chain_hot.hpp hot_fold_base); the default does nothing.
+// stage: what a wave that HAS work sets up once, around its first round of loads -- issue() in front of them, commit() behind them and
+// ahead of the first iteration (the hot program fills its sin / cos table in LDS there, chain_hot.hpp); a wave without a share of the
+// first round leaves before either.  The default does nothing.
 struct KeepTarget {
     __device__ __forceinline__ void operator()(double (&)[12]) const {}
 };
-template <int NJ, class IterFn, class TargetFn = KeepTarget>
+struct NoStage {
+    __device__ __forceinline__ void issue() {}
+    __device__ __forceinline__ void commit() {}
+};
+template <int NJ, class IterFn, class TargetFn = KeepTarget, class StageFn = NoStage>
 __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, unsigned long long *queue, int chunk_and_batch, IterFn iterate,
-                                                  TargetFn on_target = TargetFn{}) {
+                                                  TargetFn on_target = TargetFn{}, StageFn stage = StageFn{}) {
     const ChainStrides st = chain_strides(a);
     const int lane = static_cast<int>(threadIdx.x) & 63;                 // one wave per workgroup
     const int64_t first_round = static_cast<int64_t>(gridDim.x) * 64;
@@ -590,10 +597,12 @@ __device__ __forceinline__ void chain_refill_loop(const ChainKernelArgs<NJ> &a, 
     // still zero.  A thousand arrivals on one address took ~15 us, a quarter of a near-target solve.)
     const int64_t working = (nwork + 63) / 64 < static_cast<int64_t>(gridDim.x) ? (nwork + 63) / 64 : static_cast<int64_t>(gridDim.x);
     if (static_cast<int64_t>(blockIdx.x) >= working) return;
+    stage.issue();
     b = problem(have ? w0 : 0);                                          // idle lanes shadow a valid problem
 #pragma unroll
     for (int j = 0; j < NJ; ++j) q[j] = qsrc[at(st.elem, st.q_prob, a.qidx[j], b)];
     load_target(a, b, oMt);
+    stage.commit();
     on_target(oMt);
     if (listed) it = a.iters[b];                                         // (the iterations the first phase took over this problem)
     // The wave's own reserve [pool_lo, pool_hi) of unsolved problems (wave-uniform): finished lanes are served from it, and only when

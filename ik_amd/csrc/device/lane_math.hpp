@@ -28,6 +28,8 @@ template <class A, class B> struct conditional<false, A, B> { typedef B type; };
 #include <cstdint>
 #endif
 
+#include "sincos_lut_table.hpp"   // IKD_SINCOS_LUT_VALUES: the literals of dsincos_lut's table (generated, tools/gen_sincos_lut.cpp)
+
 #if defined(__HIPCC_RTC__)
 #define IKD_FN __host__ __device__ inline __attribute__((always_inline))
 #elif defined(__HIPCC__)
@@ -266,6 +268,62 @@ IKD_FN void dsincos_hot(double x, double &s_out, double &c_out) {
     s_out = s;
     c_out = c;
 }
+
+// sin and cos for the hot chain loops (device/chain_hot.hpp) from a table: x = k h + r with h = 2 pi / 1024 and k the nearest
+// integer, (S, C) = (sin, cos)(k h) read from the 1024-entry table of sincos_lut_table.hpp, and the angle-sum formulas with two-term
+// polynomials on the residual |r| <= pi / 1024 = 3.07e-3 -- no Horner chains, no angle doublings: 13 FP64 instructions, two or three
+// integer ones and one 16-byte table read against the 24 FP64 instructions of dsincos_hot.
+//     t   = fma(x, 1024 / (2 pi), 1.5 * 2^52)     round to nearest through the magic constant: t's low mantissa bits hold k
+//     kf  = t - 1.5 * 2^52                        k as a double, exact
+//     r   = fma(-kf, h_hi, x)                     h_hi = dsincos_hot's one-word 2 pi over 1024: the same 3.9e-17 |x| reduction error
+//     idx = low 32 bits of t, AND 1023            two's complement: wraps modulo 1024 for negative k; in range whatever t holds (NaN, inf)
+//     sl  = fma(r z, fma(z, 1/120, -1/6), r)      sin r, z = r^2; truncation r^7 / 5040 <= 5.1e-22
+//     cm1 = z fma(z, 1/24, -1/2)                  cos r - 1; truncation z^3 / 720 <= 1.2e-18
+//     s   = fma(C, sl, fma(S, cm1, S)),  c = fma(-S, sl, fma(C, cm1, C))
+// Error: the table entry is off by at most 2^-54 |value| <= 1.11e-16, each of the two nested FMAs rounds a value of magnitude at most 1
+// (1.11e-16 each), the relative errors of sl and cm1 enter multiplied by |r| and stay below 1e-18: 3.4e-16 + 3.9e-17 |x|, held to
+// 5e-16 + 4e-17 |x| by tests/test_sincos_lut_host.py (dsincos_hot: 2e-15).  |x| < 2^41 / 163 for the index (far beyond where the
+// reduction has any digits left).
+// In three pieces so that a caller with several angles can order them by hand -- every reduction, then every table read, then every
+// polynomial (which needs nothing from the table), then the combinations: a lone wave hides the read's latency behind nothing else.
+constexpr double kSinCosLutStepHi = 6.28318530717958623200e+00 / 1024.0;   // exact: a power of two below dsincos_hot's kTwoPiHi
+IKD_FN void dsincos_lut_reduce(double x, double &r_out, int &idx_out) {
+    constexpr double kSteps = 1024.0 * 0.15915494309189533577;   // 1024 / (2 pi)
+    constexpr double kMagic = 6755399441055744.0;                // 1.5 * 2^52
+    const double t = dfma(x, kSteps, kMagic);
+    const double kf = t - kMagic;
+    r_out = dfma(-kf, kSinCosLutStepHi, x);
+    uint64_t bits;
+    __builtin_memcpy(&bits, &t, 8);
+    idx_out = static_cast<int>(static_cast<uint32_t>(bits) & 1023u);
+}
+IKD_FN void dsincos_lut_poly(double r, double &sl_out, double &cm1_out) {
+    const double z = r * r;
+    sl_out = dfma(r * z, dfma(z, 1.0 / 120.0, -1.0 / 6.0), r);
+    cm1_out = z * dfma(z, 1.0 / 24.0, -0.5);
+}
+IKD_FN void dsincos_lut_combine(double S, double C, double sl, double cm1, double &s_out, double &c_out) {
+    s_out = dfma(C, sl, dfma(S, cm1, S));
+    c_out = dfma(-S, sl, dfma(C, cm1, C));
+}
+// fetch(idx, S, C): the table entry idx in 0 .. 1023 -- from LDS in the kernels (chain_hot.hpp), from the header's array on the host
+template <class Fetch>
+IKD_FN void dsincos_lut(double x, double &s_out, double &c_out, Fetch fetch) {
+    double r, sl, cm1, S, C;
+    int idx;
+    dsincos_lut_reduce(x, r, idx);
+    fetch(idx, S, C);
+    dsincos_lut_poly(r, sl, cm1);
+    dsincos_lut_combine(S, C, sl, cm1, s_out, c_out);
+}
+#if !IKD_ON_DEVICE
+// The host build (lane emulation under tests/) reads the header's literals directly.
+inline constexpr double kSinCosLutHost[2 * IKD_SINCOS_LUT_SIZE] = {IKD_SINCOS_LUT_VALUES};
+struct SinCosLutHostFetch {
+    void operator()(int idx, double &S, double &C) const { S = kSinCosLutHost[2 * idx]; C = kSinCosLutHost[2 * idx + 1]; }
+};
+inline void dsincos_lut(double x, double &s_out, double &c_out) { dsincos_lut(x, s_out, c_out, SinCosLutHostFetch{}); }
+#endif
 
 // acos on [-1, 1] (fdlibm e_acos rational approximation, divisions by drcp).
 IKD_FN double dacos(double x) {

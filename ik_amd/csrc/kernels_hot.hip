@@ -19,7 +19,8 @@
 namespace ikgpu {
 namespace {
 
-constexpr int kBlock = 64;  // one wave64 per workgroup: 1024 workgroups at B = 65536 cover 256 CUs x 4 SIMDs
+constexpr int kBlock = 64;  // one wave64 per workgroup: 1024 workgroups at B = 65536 cover 256 CUs x 4 SIMDs.  Every entry of chain_hot.hpp
+                            // relies on it: the 16 KB sin / cos table in static LDS is filled by one wave, 16 entries per lane, without a barrier
 
 using ikdev::ChainKernelArgs;
 using ikdev::ChainStruct;
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_track_kernel(const Chain
 }
 
 // K starts per problem in one launch, the best one stored (device/chain_hot.hpp hot_multistart_body; include/ikgpu.h
-// ikgpu_dls_multistart_batch): lane gid serves problem gid / K with start gid % K.  Lock-step; no LDS, no queue slot, no allocation.
+// ikgpu_dls_multistart_batch): lane gid serves problem gid / K with start gid % K.  Lock-step; no LDS beyond the sin / cos table, no queue slot, no allocation.
 template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP>
 __global__ __launch_bounds__(kBlock) void dls_chain_hot_multistart_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::MultistartArgs ms) {
     ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms);
@@ -64,21 +65,21 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_goalset_kernel(const Cha
 }
 
 // K starts per problem in one launch, the distinct converged ones stored (device/chain_hot.hpp hot_solutions_body; include/ikgpu.h
-// ikgpu_dls_solutions_batch): the multi-start kernel's lane mapping.  Stop rule only; lock-step; no LDS, no queue slot, no allocation.
+// ikgpu_dls_solutions_batch): the multi-start kernel's lane mapping.  Stop rule only; lock-step; no LDS beyond the sin / cos table, no queue slot, no allocation.
 template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
 __global__ __launch_bounds__(kBlock) void dls_chain_hot_solutions_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::SolutionsArgs sa) {
     ikdev::hot_solutions_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, sa);
 }
 
 // A straight Cartesian line to one goal per problem in one launch (device/chain_hot.hpp hot_line_body; include/ikgpu.h
-// ikgpu_dls_line_batch).  Stop rule only; lock-step per waypoint; no LDS, no queue slot, no allocation.
+// ikgpu_dls_line_batch).  Stop rule only; lock-step per waypoint; no LDS beyond the sin / cos table, no queue slot, no allocation.
 template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
 __global__ __launch_bounds__(kBlock) void dls_chain_hot_line_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::LineArgs la) {
     ikdev::hot_line_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, la);
 }
 
 // A Cartesian path through P vias per problem with the joint-step rule in one launch (device/chain_hot.hpp hot_path_body; include/ikgpu.h
-// ikgpu_dls_path_batch).  Stop rule only; lock-step per waypoint; no LDS, no queue slot, no allocation.
+// ikgpu_dls_path_batch).  Stop rule only; lock-step per waypoint; no LDS beyond the sin / cos table, no queue slot, no allocation.
 template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
 __global__ __launch_bounds__(kBlock) void dls_chain_hot_path_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::PathArgs pa) {
     ikdev::hot_path_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pa);

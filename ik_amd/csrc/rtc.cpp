@@ -55,6 +55,7 @@
             ".global " #sym "_end\n" #sym "_end:\n.previous\n");                                                    \
     extern "C" const char sym[];                                                                                 \
     extern "C" const char sym##_end[];
+IKGPU_EMBED(ikgpu_src_sincos_lut_table, "device/sincos_lut_table.hpp")
 IKGPU_EMBED(ikgpu_src_lane_math, "device/lane_math.hpp")
 IKGPU_EMBED(ikgpu_src_chain_solver, "device/chain_solver.hpp")
 IKGPU_EMBED(ikgpu_src_goalset, "device/goalset.hpp")
@@ -276,7 +277,8 @@ ShapeKey key_of(const ProblemHost &ph) {
 }
 
 struct Hdr { const char *name, *begin, *end; };
-const Hdr kHeaders[] = {{"lane_math.hpp", ikgpu_src_lane_math, ikgpu_src_lane_math_end},
+const Hdr kHeaders[] = {{"sincos_lut_table.hpp", ikgpu_src_sincos_lut_table, ikgpu_src_sincos_lut_table_end},
+                        {"lane_math.hpp", ikgpu_src_lane_math, ikgpu_src_lane_math_end},
                         {"chain_solver.hpp", ikgpu_src_chain_solver, ikgpu_src_chain_solver_end},
                         {"goalset.hpp", ikgpu_src_goalset, ikgpu_src_goalset_end},
                         {"line.hpp", ikgpu_src_line, ikgpu_src_line_end},

@@ -1,4 +1,5 @@
 #include <hip/hip_runtime.h>
+#define IKD_HOT_LUT_FROM_HBM   // k_evaluate hands hot_evaluate a plain HotTable: the table from HBM, asked for by name (chain_hot.hpp)
 #include "device/chain_hot.hpp"
 using namespace ikdev;
 using S = ChainStruct<355820159695091300ul, 4132432860610451030ul, 1970497541718ul>;
@@ -7,6 +8,18 @@ extern "C" __global__ void k_sincos(const double *in, double *out) {
     double s[NJ], c[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) dsincos_hot(in[j * 64 + threadIdx.x], s[j], c[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { out[(2 * j) * 64 + threadIdx.x] = s[j]; out[(2 * j + 1) * 64 + threadIdx.x] = c[j]; }
+}
+// the seven sin / cos as hot_evaluate takes them since the table: hot_sincos, the function it calls, on the table in LDS (the fill is
+// outside the FP64 column of tools/hot_phase_count.py: loads and LDS writes only)
+extern "C" __global__ __launch_bounds__(64) void k_sincos_lut(const double *in, double *out) {
+    IKD_HOT_LUT_DECLARE(t);
+    hot_lut_commit(t, hot_lut_issue(t));
+    double phi[NJ], s[NJ], c[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) phi[j] = in[j * 64 + threadIdx.x];
+    hot_sincos<NJ>(t, phi, s, c);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) { out[(2 * j) * 64 + threadIdx.x] = s[j]; out[(2 * j + 1) * 64 + threadIdx.x] = c[j]; }
 }
