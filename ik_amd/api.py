@@ -759,7 +759,8 @@ def dls_path_batch(problem, Q0, vias, data, T, max_joint_step=0.0, visitor=None,
     """Can the task frame travel from where it is at Q0 through its P via poses, T waypoints per segment, without a joint-space jump --
     and along which joint trajectory?  dls_track_batch on path_targets(problem, Q0, vias, data, T), a problem taking part in waypoint n
     only while all its earlier waypoints were met: the solve met the stop rule and, with max_joint_step > 0, no entry of the task
-    support moved by more than max_joint_step (rad, plain entries) from the configuration the solve started from.  reached[b] counts
+    support moved by more than max_joint_step (rad, or m for a prismatic joint's entry: one bound over both; plain entries) from the
+    configuration the solve started from.  reached[b] counts
     the waypoints met before the first one that was not (P T: the whole path); slabs n <= min(reached[b], P T - 1) of problem b are
     written and bit-identical to dls_track_batch on those waypoints, later slabs are unspecified; success = 1 in the failing slab says
     the waypoint was reached through a jump.  A chain problem runs one launch that reads the P vias alone.

@@ -1,5 +1,5 @@
 // chain_hot.hpp -- the headline lane program: ik::dls() for ONE problem with one Full FrameTask (unit weights, reference
-// frame fixed in the world) on a serial chain of NJ <= 7 revolute joints, specialised at compile time on the STRUCTURE of the
+// frame fixed in the world) on a serial chain of NJ <= 7 revolute or prismatic joints, specialised at compile time on the STRUCTURE of the
 // chain's constant placements.
 //
 // Same algorithm as device/chain_solver.hpp (which stays the program of every other chain problem; the reference path it
@@ -47,8 +47,12 @@ constexpr int kStructBits = 21;
 constexpr int kStructPerWord = 3;
 enum : unsigned { kEntGeneral = 0, kEntZero = 1, kEntOne = 2, kEntMinusOne = 3 };
 
-template <uint64_t C0, uint64_t C1, uint64_t C2>
+// PM: bit j set when joint j is PRISMATIC -- it slides along its local z where a revolute joint turns about it (chain_solver.hpp).
+// 0, the default, is a chain of revolute joints: the type every such chain had before prismatic joints were taken.
+template <uint64_t C0, uint64_t C1, uint64_t C2, unsigned PM = 0>
 struct ChainStruct {
+    static constexpr unsigned kPrismatic = PM;
+    static constexpr bool prismatic(int j) { return j >= 0 && ((PM >> j) & 1u) != 0; }
     static constexpr uint64_t word(int w) { return w == 0 ? C0 : (w == 1 ? C1 : C2); }
     static constexpr unsigned code(int i) { return static_cast<unsigned>((word(i / kStructPerWord) >> (kStructBits * (i % kStructPerWord))) & 0x1fffffu); }
     static constexpr unsigned ent(int i, int e) { return (code(i) >> (2 * e)) & 3u; }           // e = 3 m + k
@@ -64,11 +68,12 @@ struct ChainStruct {
     static constexpr double literal(int i, int e) { return ent(i, e) == kEntOne ? 1.0 : (ent(i, e) == kEntMinusOne ? -1.0 : 0.0); }
     // Joint j (>= 1) turns about the SAME world axis as joint j - 1 when its placement has an exactly-identity rotation (R * Rz leaves
     // the third column of R alone).  leader(j): the first joint of j's run of parallel axes; members(L): how many joints L leads.
+    // A prismatic joint has no angle to share: it is a run of its own and ends the run below it (leader(j) = j for it and for j + 1).
     static constexpr bool identity_rotation(int i) {
         return ent(i, 0) == kEntOne && ent(i, 4) == kEntOne && ent(i, 8) == kEntOne && ent(i, 1) == kEntZero && ent(i, 2) == kEntZero &&
                ent(i, 3) == kEntZero && ent(i, 5) == kEntZero && ent(i, 6) == kEntZero && ent(i, 7) == kEntZero;
     }
-    static constexpr int leader(int j) { return (j > 0 && identity_rotation(j)) ? leader(j - 1) : j; }
+    static constexpr int leader(int j) { return (j > 0 && identity_rotation(j) && !prismatic(j) && !prismatic(j - 1)) ? leader(j - 1) : j; }
     static constexpr int members(int L, int nj) { return nj <= 0 ? 0 : members(L, nj - 1) + (leader(nj - 1) == L ? 1 : 0); }
 };
 
@@ -90,10 +95,10 @@ constexpr int kHotFoldMinRun = 2;
 // the tip-side end of its run (the member the tip-to-base walk meets first); any_folded: the chain has a folded run.
 template <class S, int NJ>
 struct ChainRuns {
-    struct Table { int leader[8], members[8]; bool folded[8], tip[8], any_folded; };
+    struct Table { int leader[8], members[8]; bool folded[8], tip[8], prismatic[8], any_folded; };
     static constexpr Table make() {
         Table t{};
-        for (int j = 0; j < 8; ++j) { t.leader[j] = j < NJ ? S::leader(j) : j; t.members[j] = 0; }
+        for (int j = 0; j < 8; ++j) { t.leader[j] = j < NJ ? S::leader(j) : j; t.members[j] = 0; t.prismatic[j] = j < NJ && S::prismatic(j); }
         for (int j = 0; j < NJ; ++j) ++t.members[t.leader[j]];
         for (int j = 0; j < 8; ++j) {
             t.folded[j] = t.members[t.leader[j]] >= kHotFoldMinRun;
@@ -188,19 +193,24 @@ IKD_FN void hot_lut_fetch(const HotTable &, int idx, double &S, double &C) {
 // dsincos_lut in its pieces, ordered by hand because a lone wave hides the table read behind nothing else -- every reduction and
 // index, then the NJ reads in the order the tip-to-base walk consumes them, then the residual polynomials, which need nothing from
 // the table, then the combinations.
-template <int NJ, class Tab>
+// PM: the chain's prismatic joints (ChainStruct) -- no angle, so nothing is computed for them and sn / cs stay unset there.
+template <int NJ, unsigned PM = 0, class Tab>
 IKD_FN void hot_sincos(const Tab &t, const double (&phi)[NJ], double (&sn)[NJ], double (&cs)[NJ]) {
     double res[NJ], tS[NJ], tC[NJ], sl[NJ], cm1[NJ];
     int idx[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) dsincos_lut_reduce(phi[j], res[j], idx[j]);
+    for (int j = 0; j < NJ; ++j)
+        if (!((PM >> j) & 1u)) dsincos_lut_reduce(phi[j], res[j], idx[j]);
 #pragma unroll
-    for (int j = NJ - 1; j >= 0; --j) hot_lut_fetch(t, idx[j], tS[j], tC[j]);
+    for (int j = NJ - 1; j >= 0; --j)
+        if (!((PM >> j) & 1u)) hot_lut_fetch(t, idx[j], tS[j], tC[j]);
     IKD_SCHED_FENCE();   // (left alone the scheduler issues the reads behind the polynomials and waits for them at once)
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) dsincos_lut_poly(res[j], sl[j], cm1[j]);
+    for (int j = 0; j < NJ; ++j)
+        if (!((PM >> j) & 1u)) dsincos_lut_poly(res[j], sl[j], cm1[j]);
 #pragma unroll
-    for (int j = NJ - 1; j >= 0; --j) dsincos_lut_combine(tS[j], tC[j], sl[j], cm1[j], sn[j], cs[j]);
+    for (int j = NJ - 1; j >= 0; --j)
+        if (!((PM >> j) & 1u)) dsincos_lut_combine(tS[j], tC[j], sl[j], cm1[j], sn[j], cs[j]);
 }
 
 // entry e = 3 m + k of placement I's rotation: the literal 0.0 / +-1.0 when structural, else its table value
@@ -291,7 +301,7 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
     double phi[NJ], sn[NJ], cs[NJ];
 #pragma unroll
     for (int j = NJ - 1; j >= 0; --j) phi[j] = (kRuns.folded[j] && !kRuns.tip[j]) ? phi[j + 1 < NJ ? j + 1 : j] + q[j] : q[j];
-    hot_sincos<NJ>(t, phi, sn, cs);
+    hot_sincos<NJ, S::kPrismatic>(t, phi, sn, cs);
 
     double ang[NJ][3], lin[NJ][3];
     double rows[NJ][6], pt[NJ][2];   // folded runs: rows 0 and 1 of R at the run's entry (by leader), p~0 and p~1 (by member)
@@ -313,7 +323,14 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
     if (J < NJ) {                                                                                          \
         constexpr int jj = J < NJ ? J : 0;                                                                 \
         ang[jj][0] = R[6]; ang[jj][1] = R[7]; ang[jj][2] = R[8];                                           \
-        if (!kRuns.folded[jj]) {                                                                           \
+        if (kRuns.prismatic[jj]) {                                                                         \
+            /* the unit translation along z carried to the task frame: linear part R^T e_z, no angular part (the column loop    \
+               below never reads ang of a prismatic joint); then Y <- P_J Trans_z(q_J) Y */                \
+            lin[jj][0] = R[6]; lin[jj][1] = R[7]; lin[jj][2] = R[8];                                       \
+            p[2] += q[jj];                                                                                 \
+            if (!(BASE_FOLDED && jj == 0)) hot_compose_left<S, jj>(R, p, t);                               \
+            if (kPinWalk) { IKD_PIN(p[0]); IKD_PIN(p[1]); IKD_PIN(p[2]); IKD_PIN(R[0]); }                  \
+        } else if (!kRuns.folded[jj]) {                                                                    \
             lin[jj][0] = dfma(p[0], R[3], -(p[1] * R[0]));                                                 \
             lin[jj][1] = dfma(p[0], R[4], -(p[1] * R[1]));                                                 \
             lin[jj][2] = dfma(p[0], R[5], -(p[1] * R[2]));                                                 \
@@ -385,6 +402,14 @@ IKD_FN void hot_evaluate(const Tab &t, const double (&q)[NJ], const double (&oMt
     // top = A lin_j + C beta_j.  The product C A is never formed.  In a folded run A lin_j = p~0 (A r1) - p~1 (A r0).
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
+        if (kRuns.prismatic[j]) {   // [A lin_j ; 0]: beta_j = 0, written as the literal
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                col[j][i] = dfma(lj.A[3 * i], lin[j][0], dfma(lj.A[3 * i + 1], lin[j][1], lj.A[3 * i + 2] * lin[j][2]));
+                col[j][3 + i] = 0.0;
+            }
+            continue;
+        }
         double beta[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) beta[i] = dfma(lj.A[3 * i], ang[j][0], dfma(lj.A[3 * i + 1], ang[j][1], lj.A[3 * i + 2] * ang[j][2]));
@@ -439,7 +464,7 @@ IKD_FN void hot_gram(const double (&col)[NJ][6], double lam2, double (&G)[36]) {
                     double s = 0.0;
     #pragma unroll
                     for (int j = 0; j < NJ; ++j)
-                        if (kRuns.leader[j] == j) s = dfma(col[j][a], top_sum[j][b], s);
+                        if (kRuns.leader[j] == j && !kRuns.prismatic[j]) s = dfma(col[j][a], top_sum[j][b], s);   // (a prismatic column has no angular rows)
                     G[a * M + b] = s;
                 }
     #pragma unroll
@@ -447,7 +472,7 @@ IKD_FN void hot_gram(const double (&col)[NJ][6], double lam2, double (&G)[36]) {
                     double s = (a == b) ? lam2 : 0.0;
     #pragma unroll
                     for (int j = 0; j < NJ; ++j)
-                        if (kRuns.leader[j] == j) s = dfma(nbot[j][a - 3], col[j][b], s);
+                        if (kRuns.leader[j] == j && !kRuns.prismatic[j]) s = dfma(nbot[j][a - 3], col[j][b], s);
                     G[a * M + b] = s;
                 }
             }
@@ -461,10 +486,10 @@ IKD_FN void hot_step(const Tab &t, const LoopParams &prm, const double (&col)[NJ
     double ang[NJ];   // the angular part of col_j^T y, shared by a run of parallel axes
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
-        if (kRuns.leader[j] == j) ang[j] = dfma(col[j][3], y[3], dfma(col[j][4], y[4], col[j][5] * y[5]));
+        if (kRuns.leader[j] == j && !kRuns.prismatic[j]) ang[j] = dfma(col[j][3], y[3], dfma(col[j][4], y[4], col[j][5] * y[5]));
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        double s = ang[kRuns.leader[j]];
+        double s = kRuns.prismatic[j] ? 0.0 : ang[kRuns.leader[j]];
 #pragma unroll
         for (int a = 0; a < 3; ++a) s = dfma(col[j][a], y[a], s);
         const double qn = dfma(prm.step_length, s, q[j]);  // dq_j = -J_task(:, j)^T y = +col_j^T y
@@ -702,7 +727,7 @@ IKD_FN int hot_line_body(const ChainKernelArgs<NJ> &a, const Tab &t, const LineA
     hot_lut_commit(t, lut_stage);
     LineStart ls;
     typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
-    line_chain_start(a, *(ConstDesc *)a.desc, q, goal, ls);
+    line_chain_start<S::kPrismatic != 0>(a, *(ConstDesc *)a.desc, q, goal, ls);
     bool alive = true, stepped = false;
     int reached = 0, k = 0;
     for (; k < la.T && IKD_ANY(alive); ++k) {
@@ -744,7 +769,7 @@ IKD_FN int hot_path_body(const ChainKernelArgs<NJ> &a, const Tab &t, const PathA
     hot_lut_commit(t, lut_stage);
     LineStart ls;
     typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
-    line_chain_start(a, *(ConstDesc *)a.desc, q, via, ls);
+    line_chain_start<S::kPrismatic != 0>(a, *(ConstDesc *)a.desc, q, via, ls);
     bool alive = true, stepped = false;
     int reached = 0;
     int64_t n = 0;

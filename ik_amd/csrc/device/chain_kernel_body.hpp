@@ -232,10 +232,10 @@ IKD_FN void line_load(const ChainKernelArgs<NJ> &a, int64_t b, double (&q)[NJ], 
     load_target_raw(a, a.targets, b, goal);
 }
 // The start of the line of a chain problem: FK at q from the chain table in HBM (a.desc), through scalar loads on the device.
-template <int NJ, class Desc>
+template <bool KINDS = false, int NJ, class Desc>
 IKD_FN void line_chain_start(const ChainKernelArgs<NJ> &a, const Desc &d, const double (&q)[NJ], const double (&goal)[12], LineStart &ls) {
     double Rf[9], pf[3];
-    line_chain_fk<NJ>(d, a.prm.idmask, q, Rf, pf);
+    line_chain_fk<NJ, KINDS>(d, a.prm.idmask, q, Rf, pf);
     line_start(a.ref_pl, Rf, pf, goal, ls);
 }
 
@@ -248,7 +248,7 @@ IKD_FN int dls_chain_line_body(const ChainKernelArgs<NJ> &a, const Desc &d, cons
     double q[NJ], goal[12];
     line_load(a, b, q, goal);
     LineStart ls;
-    line_chain_start(a, d, q, goal, ls);
+    line_chain_start<ReadsKinds<SMASK>::value>(a, d, q, goal, ls);
     bool alive = true, stepped = false;
     int reached = 0, k = 0;
     for (; k < la.T && IKD_ANY(alive); ++k) {
@@ -300,7 +300,7 @@ IKD_FN int dls_chain_path_body(const ChainKernelArgs<NJ> &a, const Desc &d, cons
     double q[NJ], q_prev[NJ], via[12], next[12];
     line_load(a, b, q, via);
     LineStart ls;
-    line_chain_start(a, d, q, via, ls);
+    line_chain_start<ReadsKinds<SMASK>::value>(a, d, q, via, ls);
     bool alive = true, stepped = false;
     int reached = 0;
     int64_t n = 0;
@@ -687,7 +687,7 @@ __device__ __forceinline__ void dls_chain_refill_body(const ChainKernelArgs<NJ> 
 // evaluate_problem_data + stacking (reference ik/ik/data.cpp:25-58, ik/ik/dls.cpp:18-24):
 // e [M x B], dense J [M x nv x B] (zero outside the support, as the reference's zero-initialised
 // frame Jacobian, ik/ik/frame.hpp:110).
-template <int NJ, int KT>
+template <int NJ, int KT, int SMASK = -1>
 IKD_FN void eval_chain_body(const ChainKernelArgs<NJ> &a, const ChainDesc<NJ> &d, int64_t b) {
     constexpr int M = TaskDim<KT>::value;
     if (b >= a.B) return;
@@ -697,7 +697,7 @@ IKD_FN void eval_chain_body(const ChainKernelArgs<NJ> &a, const ChainDesc<NJ> &d
     double oMt[12];
     load_target(a, b, oMt);
     double e[M], col[NJ][M], Rf[9], pf[3];
-    chain_evaluate<NJ, KT>(d, q, oMt, a.prm.idmask, a.prm.unit_weights != 0, e, col, Rf, pf);
+    chain_evaluate<NJ, KT, SMASK>(d, q, oMt, a.prm.idmask, a.prm.unit_weights != 0, e, col, Rf, pf);
 #pragma unroll
     for (int r = 0; r < M; ++r) a.e_out[at(a.layout, a.B, M, r, b)] = e[r];
     if (a.J_out) {
@@ -711,7 +711,7 @@ IKD_FN void eval_chain_body(const ChainKernelArgs<NJ> &a, const ChainDesc<NJ> &d
 }
 
 // World placement of the task frame (reference ik/ik/data.cpp:28-29, one entry of data.oMf).
-template <int NJ>
+template <int NJ, bool KINDS = false>
 IKD_FN void fk_chain_body(const ChainKernelArgs<NJ> &a, const ChainDesc<NJ> &d, int64_t b) {
     if (b >= a.B) return;
     double R[9], p[3];
@@ -722,9 +722,18 @@ IKD_FN void fk_chain_body(const ChainKernelArgs<NJ> &a, const ChainDesc<NJ> &d, 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (j > 0) se3_compose_const(R, p, d.pl[j], (a.prm.idmask >> j) & 1);
-        double s, c;
-        dsincos(a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)], s, c);
-        rot_z_right(R, s, c);
+        const double qj = a.q0[at(a.layout, a.B, a.nq, a.qidx[j], b)];
+        bool slides = false;
+        if constexpr (KINDS) slides = ((a.prm.idmask >> (kKindShift + j)) & 1) != 0;
+        if (slides) {
+            p[0] = dfma(qj, R[2], p[0]);
+            p[1] = dfma(qj, R[5], p[1]);
+            p[2] = dfma(qj, R[8], p[2]);
+        } else {
+            double s, c;
+            dsincos(qj, s, c);
+            rot_z_right(R, s, c);
+        }
     }
     se3_compose_const(R, p, d.frame_pl, (a.prm.idmask >> NJ) & 1);
 #pragma unroll

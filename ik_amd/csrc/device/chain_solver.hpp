@@ -14,7 +14,9 @@
 //
 // Every joint is "revolute about local z": an arbitrary unit axis a is folded into the constant
 // placements on the host (pl' = P_prev^T pl P, P e_z = a), which leaves oMi * a and the joint
-// origin -- all the Jacobian needs -- unchanged.
+// origin -- all the Jacobian needs -- unchanged.  A prismatic joint slides ALONG its local z after the same folding: Trans_z(q_j)
+// where a revolute joint has Rot_z(q_j), column [z_j ; 0] where a revolute joint has [(o_j - p_f) x z_j ; z_j].  Only the builds
+// that read the joint-kind mask (kSpecKinds below) know of them; a chain of revolute joints never runs one.
 #pragma once
 #if !defined(__HIPCC_RTC__)
 #include <type_traits>
@@ -40,7 +42,8 @@ struct LoopParams {
     double step_length;
     double stop_sq_tol;  // < 0: never stop
     int priority;        // priority level of the task (the stop test reads priority-0 rows only)
-    int idmask;          // bit j: placement pl[j] has an exactly-identity rotation; bit NJ: frame_pl has
+    int idmask;          // bit j: placement pl[j] has an exactly-identity rotation; bit NJ: frame_pl has;
+                         // bit kKindShift + j: joint j is prismatic (read by the builds with kSpecKinds only; 0: all revolute)
     int unit_weights;    // every Task::weighting() entry is exactly 1
     // derived-visitor family (include/ikgpu.h ikgpu_dls_params; read by the generic lane program only -- a solve that uses them is
     // routed there): dq_sq_tol > 0: also stop when ||dq||^2 < dq_sq_tol; nlt > 0: the error test is ||e[l]||^2 < lvl_tol[l], all l < nlt
@@ -50,6 +53,16 @@ struct LoopParams {
 };
 
 constexpr int kSpecUnit = 30;
+// Joint kinds.  SMASK bit kSpecKinds (compile-time builds), or SMASK = kSpecRuntimeKinds (the runtime-parameter build: stage kernels,
+// host emulation): the build reads the wave-uniform joint-kind mask in bits kKindShift.. of LoopParams::idmask -- a kernel argument, so
+// the per-joint choice is a scalar branch.  Taken only for a chain with a prismatic joint; every other build has no such branch.
+constexpr int kSpecKinds = 29;
+constexpr int kSpecRuntimeKinds = -2;
+constexpr int kKindShift = 16;
+template <int SMASK>
+struct ReadsKinds {
+    static constexpr bool value = SMASK == kSpecRuntimeKinds || (SMASK >= 0 && ((SMASK >> kSpecKinds) & 1) != 0);
+};
 
 template <int KT>
 struct TaskDim {
@@ -60,7 +73,7 @@ struct TaskDim {
 // the minus sign of reference ik/ik/frame.hpp:173-181 is folded into the step, dq = +col^T y) at configuration q.
 // oMt: target placement in the world (reference frame fixed in the world), 12 doubles.
 // SMASK >= 0: specialisation known at compile time -- bits 0..NJ: identity-rotation placement mask (must be a subset
-// of the problem's mask), bit kSpecUnit: every weight is exactly 1.  SMASK = -1: take the wave-uniform runtime values
+// of the problem's mask), bit kSpecUnit: every weight is exactly 1.  SMASK < 0: take the wave-uniform runtime values
 // `idmask` / `unit_weights`.  A compile-time value keeps the whole iteration one basic block, so the scheduler can
 // hoist the LDS reads of the constant table far ahead of their use -- with one wave per SIMD nothing else hides that
 // latency (measured: s_waitcnt stalls were 17 % of wave cycles with runtime branches; +18 % solves/s without them).
@@ -70,6 +83,7 @@ IKD_FN void chain_evaluate(const Desc &d, const double (&q)[NJ], const double (&
                            bool unit_weights, double (&e)[TaskDim<KT>::value], double (&col)[NJ][TaskDim<KT>::value],
                            double (&Rf)[9], double (&pf)[3]) {
     constexpr int M = TaskDim<KT>::value;
+    constexpr bool kKinds = ReadsKinds<SMASK>::value;
     double zax[NJ][3], org[NJ][3];
     double R[9], p[3];
 #pragma unroll
@@ -79,10 +93,18 @@ IKD_FN void chain_evaluate(const Desc &d, const double (&q)[NJ], const double (&
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (j > 0) se3_compose_const(R, p, d.pl[j], SMASK >= 0 ? ((SMASK >> j) & 1) != 0 : ((idmask >> j) & 1) != 0);
-        double s, c;
-        if constexpr (SMASK < 0) dsincos(q[j], s, c);  // stage kernels and the runtime-parameter build
-        else dsincos_fast(q[j], s, c);                 // the device's iteration loops
-        rot_z_right(R, s, c);
+        bool slides = false;
+        if constexpr (kKinds) slides = ((idmask >> (kKindShift + j)) & 1) != 0;   // wave-uniform
+        if (slides) {  // Trans_z(q_j): p += q_j R[:, 2]
+            p[0] = dfma(q[j], R[2], p[0]);
+            p[1] = dfma(q[j], R[5], p[1]);
+            p[2] = dfma(q[j], R[8], p[2]);
+        } else {
+            double s, c;
+            if constexpr (SMASK < 0) dsincos(q[j], s, c);  // stage kernels and the runtime-parameter build
+            else dsincos_fast(q[j], s, c);                 // the device's iteration loops
+            rot_z_right(R, s, c);
+        }
         zax[j][0] = R[2]; zax[j][1] = R[5]; zax[j][2] = R[8];
         org[j][0] = p[0]; org[j][1] = p[1]; org[j][2] = p[2];
     }
@@ -172,6 +194,20 @@ IKD_FN void chain_evaluate(const Desc &d, const double (&q)[NJ], const double (&
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
+        if constexpr (kKinds) {
+            if (((idmask >> (kKindShift + j)) & 1) != 0) {  // J_local(:, j) = [Rf^T z_j ; 0]: the origin is not read
+                if (KT == KT_FULL || KT == KT_POSITION) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+                        col[j][i] = dfma(AtR[3 * i], zax[j][0], dfma(AtR[3 * i + 1], zax[j][1], AtR[3 * i + 2] * zax[j][2]));
+                }
+                if (KT == KT_FULL || KT == KT_ORIENTATION) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) col[j][((KT == KT_FULL) ? 3 : 0) + i] = 0.0;
+                }
+                continue;
+            }
+        }
         const double dj[3] = {org[j][0] - p[0], org[j][1] - p[1], org[j][2] - p[2]};
         double vw[3];
         cross(dj, zax[j], vw);

@@ -72,8 +72,8 @@ IKD_FN void exp3(const double (&w)[3], double (&R)[9]) {
 }
 
 // World placement of a chain's task frame at q: the arithmetic of the stage kernel (chain_kernel_body.hpp fk_chain_body: dsincos, the
-// run-time placement mask), on the lane's own copy of the chain entries.
-template <int NJ, class Desc>
+// run-time placement mask), on the lane's own copy of the chain entries.  KINDS: read the joint-kind mask (chain_solver.hpp kKindShift).
+template <int NJ, bool KINDS = false, class Desc>
 IKD_FN void line_chain_fk(const Desc &d, int idmask, const double (&q)[NJ], double (&R)[9], double (&p)[3]) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = d.pl[0][k];
@@ -82,9 +82,17 @@ IKD_FN void line_chain_fk(const Desc &d, int idmask, const double (&q)[NJ], doub
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (j > 0) se3_compose_const(R, p, d.pl[j], ((idmask >> j) & 1) != 0);
-        double s, c;
-        dsincos(q[j], s, c);
-        rot_z_right(R, s, c);
+        bool slides = false;
+        if constexpr (KINDS) slides = ((idmask >> (16 + j)) & 1) != 0;
+        if (slides) {
+            p[0] = dfma(q[j], R[2], p[0]);
+            p[1] = dfma(q[j], R[5], p[1]);
+            p[2] = dfma(q[j], R[8], p[2]);
+        } else {
+            double s, c;
+            dsincos(q[j], s, c);
+            rot_z_right(R, s, c);
+        }
     }
     se3_compose_const(R, p, d.frame_pl, ((idmask >> NJ) & 1) != 0);
 }

@@ -87,7 +87,8 @@ __global__ __launch_bounds__(kBlock) void dls_chain_line_kernel(const ChainKerne
 }
 
 // The waypoints of ikgpu_line_targets for a chain problem: a.targets holds the goals, a.oMf_out the T slabs.
-template <int NJ>
+// KINDS: the chain has a prismatic joint (device/chain_solver.hpp kKindShift), here and in the stage kernels below.
+template <int NJ, bool KINDS>
 __global__ __launch_bounds__(kBlock) void line_targets_chain_kernel(const ChainKernelArgs<NJ> a, const int T) {
     const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (b >= a.B) return;
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(kBlock) void line_targets_chain_kernel(const ChainK
     double q[NJ], goal[12];
     ikdev::line_load(a, b, q, goal);
     ikdev::LineStart ls;
-    ikdev::line_chain_start(a, *(ConstDesc *)a.desc, q, goal, ls);
+    ikdev::line_chain_start<KINDS>(a, *(ConstDesc *)a.desc, q, goal, ls);
     for (int k = 0; k < T; ++k) {
         double t[12];
         ikdev::line_waypoint(ls, goal, k, T, t);
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void dls_chain_path_kernel(const ChainKerne
 }
 
 // The waypoints of ikgpu_path_targets for a chain problem: a.targets holds the P slabs of vias, a.oMf_out the P x T slabs.
-template <int NJ>
+template <int NJ, bool KINDS>
 __global__ __launch_bounds__(kBlock) void path_targets_chain_kernel(const ChainKernelArgs<NJ> a, const int P, const int T) {
     const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (b >= a.B) return;
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(kBlock) void path_targets_chain_kernel(const ChainK
     double q[NJ], via[12];
     ikdev::line_load(a, b, q, via);
     ikdev::LineStart ls;
-    ikdev::line_chain_start(a, *(ConstDesc *)a.desc, q, via, ls);
+    ikdev::line_chain_start<KINDS>(a, *(ConstDesc *)a.desc, q, via, ls);
     for (int s = 0; s < P; ++s) {
         if (s > 0) {
             double next[12];
@@ -366,18 +367,18 @@ __global__ __launch_bounds__(256) void chain_pass_through_kernel(const PassThrou
     }
 }
 
-template <int NJ, int KT>
+template <int NJ, int KT, int SMASK>
 __global__ __launch_bounds__(kBlock) void eval_chain_kernel(const ChainKernelArgs<NJ> a) {
     __shared__ double lds_desc[sizeof(ChainDesc<NJ>) / sizeof(double)];
     const ChainDesc<NJ> &d = stage_desc<NJ>(a.desc, lds_desc);
-    ikdev::eval_chain_body<NJ, KT>(a, d, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
+    ikdev::eval_chain_body<NJ, KT, SMASK>(a, d, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
 }
 
-template <int NJ>
+template <int NJ, bool KINDS>
 __global__ __launch_bounds__(kBlock) void fk_chain_kernel(const ChainKernelArgs<NJ> a) {
     __shared__ double lds_desc[sizeof(ChainDesc<NJ>) / sizeof(double)];
     const ChainDesc<NJ> &d = stage_desc<NJ>(a.desc, lds_desc);
-    ikdev::fk_chain_body<NJ>(a, d, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
+    ikdev::fk_chain_body<NJ, KINDS>(a, d, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
 }
 
 template <int NJ>
@@ -408,8 +409,11 @@ hipError_t run_dls_build(const ProblemHost &ph, const DeviceTables &dt, const Ba
 // neither has a branch inside the iteration ... and, for the shapes with a known mask, one in between: the mask folded, the weights
 // applied (a weighted task on a Cassie leg or a UR arm keeps the skipped placement products).  Every kind of job takes its kernel from
 // this one choice, which is what makes a tracking or multi-start launch return the single solve's bits.
+// A chain with a prismatic joint takes one build of its own: nothing skipped, weights applied, the joint-kind mask read from the
+// kernel arguments (device/chain_solver.hpp kSpecKinds).  No other build knows of joint kinds.
 template <int NJ, class F>
 hipError_t with_chain_build(int idmask, bool unit_weights, F f) {
+    if ((idmask >> ikdev::kKindShift) != 0) return f(std::integral_constant<int, (1 << ikdev::kSpecKinds)>{});
     constexpr int kMask = HotMask<NJ>::value;
     constexpr int kHot = kMask | (1 << ikdev::kSpecUnit);
     if constexpr (kMask != 0) {
@@ -451,7 +455,8 @@ hipError_t run_eval(const ProblemHost &ph, const DeviceTables &dt, int64_t B, co
     a.targets = targets;
     a.e_out = e_out;
     a.J_out = J_out;
-    hipLaunchKernelGGL((eval_chain_kernel<NJ, KT>), grid_for(B), dim3(kBlock), 0, stream, a);
+    if ((a.prm.idmask >> ikdev::kKindShift) != 0) hipLaunchKernelGGL((eval_chain_kernel<NJ, KT, ikdev::kSpecRuntimeKinds>), grid_for(B), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL((eval_chain_kernel<NJ, KT, -1>), grid_for(B), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -463,7 +468,8 @@ hipError_t run_fk(const ProblemHost &ph, const DeviceTables &dt, int64_t B, cons
     a.B = B;
     a.q0 = q;
     a.oMf_out = oMf_out;
-    hipLaunchKernelGGL((fk_chain_kernel<NJ>), grid_for(B), dim3(kBlock), 0, stream, a);
+    if ((a.prm.idmask >> ikdev::kKindShift) != 0) hipLaunchKernelGGL((fk_chain_kernel<NJ, true>), grid_for(B), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL((fk_chain_kernel<NJ, false>), grid_for(B), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -613,7 +619,8 @@ hipError_t launch_line_targets_chain(const ProblemHost &ph, const DeviceTables &
     if (nj == N) {                                                                                           \
         ChainKernelArgs<N> a = make_args<N>(ph, dt);                                                         \
         a.layout = layout; a.B = B; a.q0 = q0; a.targets = goals; a.oMf_out = out;                           \
-        hipLaunchKernelGGL((line_targets_chain_kernel<N>), grid_for(B), dim3(kBlock), 0, stream, a, T);      \
+        if (ph.chain.prismatic) hipLaunchKernelGGL((line_targets_chain_kernel<N, true>), grid_for(B), dim3(kBlock), 0, stream, a, T); \
+        else hipLaunchKernelGGL((line_targets_chain_kernel<N, false>), grid_for(B), dim3(kBlock), 0, stream, a, T); \
         return hipGetLastError();                                                                            \
     }
     IKGPU_FOR_NJ(X)
@@ -641,7 +648,8 @@ hipError_t launch_path_targets_chain(const ProblemHost &ph, const DeviceTables &
     if (nj == N) {                                                                                           \
         ChainKernelArgs<N> a = make_args<N>(ph, dt);                                                         \
         a.layout = layout; a.B = B; a.q0 = q0; a.targets = vias; a.oMf_out = out;                            \
-        hipLaunchKernelGGL((path_targets_chain_kernel<N>), grid_for(B), dim3(kBlock), 0, stream, a, P, T);   \
+        if (ph.chain.prismatic) hipLaunchKernelGGL((path_targets_chain_kernel<N, true>), grid_for(B), dim3(kBlock), 0, stream, a, P, T); \
+        else hipLaunchKernelGGL((path_targets_chain_kernel<N, false>), grid_for(B), dim3(kBlock), 0, stream, a, P, T); \
         return hipGetLastError();                                                                            \
     }
     IKGPU_FOR_NJ(X)

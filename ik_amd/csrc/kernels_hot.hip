@@ -103,7 +103,9 @@ static bool chain_hot_eligible(const ProblemHost &ph) {
 bool chain_hot_built(const ProblemHost &ph) {
     if (!chain_hot_eligible(ph)) return false;
     const ChainStructure &s = ph.chain_struct;
-    if (!s.fits) return false;
+    // The pre-built programs are chains of revolute joints.  The structure code does not say which joints slide: a UR5 whose elbow
+    // is prismatic has UR5's code, and takes the run-time compiled build (whose key carries the mask) like any other chain.
+    if (!s.fits || s.prismatic != 0) return false;
 #define X(N, K0, K1, K2) \
     if (ph.chain.nj == N && s.code[0] == K0 && s.code[1] == K1 && s.code[2] == K2) return true;
     IKGPU_HOT_SHAPES(X)

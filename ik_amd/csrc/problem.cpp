@@ -41,10 +41,11 @@ int task_dim(const ikgpu_task &t) {  // align / posture rows: 1; frame position 
 
 bool is_identity(const SE3 &s) { return s == se3_identity(); }
 
-// Axis-folded table of the revolute joints `joints` (root first) ending in frame `frame`.
+// Axis-folded table of the joints `joints` (root first) ending in frame `frame`: revolute, or with `prismatic_ok` prismatic as well
+// (the same folding: the joint then slides along its local z).
 // pl[0] is relative to the parent joint of joints[0] (the universe, or the free-flyer base).
 ChainHost build_chain(const Model &m, const std::vector<int> &joints, int frame, int task_index,
-                      std::vector<uint8_t> &q_in_chain) {
+                      std::vector<uint8_t> &q_in_chain, bool prismatic_ok) {
     if (static_cast<int>(joints.size()) > kMaxChain)
         throw std::runtime_error("unsupported on the device yet: support chain longer than " + std::to_string(kMaxChain) + " joints");
     ChainHost c;
@@ -53,8 +54,10 @@ ChainHost build_chain(const Model &m, const std::vector<int> &joints, int frame,
     double Pprev[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     for (int k = 0; k < c.nj; ++k) {
         const int j = joints[k];
-        if (m.joint_type[j] != IKGPU_JOINT_REVOLUTE)
+        const bool slides = prismatic_ok && m.joint_type[j] == IKGPU_JOINT_PRISMATIC;
+        if (m.joint_type[j] != IKGPU_JOINT_REVOLUTE && !slides)
             throw std::runtime_error("unsupported on the device yet: joint '" + m.joint_names[j] + "' in the task support is not revolute");
+        if (slides) c.prismatic |= 1 << k;
         if (q_in_chain[m.joint_idx_q[j]])
             throw std::runtime_error("unsupported on the device yet: joint '" + m.joint_names[j] + "' is in the support of two tasks");
         double P[9];
@@ -102,13 +105,15 @@ void specialise(ProblemHost &ph, const Model &m) {
         if (m.joint_type[j] == IKGPU_JOINT_REVOLUTE_UNBOUNDED) throw Unsupported("a model with continuous joints runs on the generic kernel");
     std::vector<uint8_t> in_chain(m.nq, 0);
 
-    auto chain_of = [&](const std::vector<int> &joints, int frame, int task_index) {
+    // prismatic_ok: the single-chain kind takes sliding joints; the chains of the tree kind stay revolute
+    auto chain_of = [&](const std::vector<int> &joints, int frame, int task_index, bool prismatic_ok = false) {
         if (static_cast<int>(joints.size()) > kMaxChain) throw Unsupported("support chain longer than the specialised kernels take");
         for (int j : joints) {
-            if (m.joint_type[j] != IKGPU_JOINT_REVOLUTE) throw Unsupported("non-revolute joint in a task support");
+            if (m.joint_type[j] != IKGPU_JOINT_REVOLUTE && !(prismatic_ok && m.joint_type[j] == IKGPU_JOINT_PRISMATIC))
+                throw Unsupported("non-revolute joint in a task support");
             if (in_chain[m.joint_idx_q[j]]) throw Unsupported("a joint is in the support of two tasks");
         }
-        return build_chain(m, joints, frame, task_index, in_chain);
+        return build_chain(m, joints, frame, task_index, in_chain, prismatic_ok);
     };
 
     if (!ph.constraints.empty() && !free_flyer) throw Unsupported("a constraint on a fixed-base model runs on the generic kernel");
@@ -119,7 +124,7 @@ void specialise(ProblemHost &ph, const Model &m) {
         std::vector<int> joints;
         for (int j = m.frame_parent[t.frame]; j > 0; j = m.joint_parent[j]) joints.insert(joints.begin(), j);
         if (joints.empty()) throw Unsupported("task frame fixed in the world");
-        ph.chain = chain_of(joints, t.frame, 0);
+        ph.chain = chain_of(joints, t.frame, 0, /*prismatic_ok=*/true);
         ph.chain_struct = chain_structure(ph.chain);
         ph.chain_hot = chain_hot_table(ph.chain);
         ph.kind = KernelKind::Chain;
@@ -621,8 +626,11 @@ int chain_identity_mask(const ChainHost &c) {
     return m;
 }
 
+int chain_kernel_mask(const ChainHost &c) { return chain_identity_mask(c) | (c.prismatic << 16); }
+
 ChainStructure chain_structure(const ChainHost &c) {
     ChainStructure out;
+    out.prismatic = c.prismatic;
     if (c.nj < 1 || c.nj > 7) return out;
     out.fits = true;
     for (int i = 0; i <= c.nj; ++i) {
@@ -671,7 +679,7 @@ void fill_chain_args(const ProblemHost &ph, double *ref_pl12, int *qidx, int *vi
     *nq = ph.nq;
     *nv = ph.nv;
     *priority = ph.tasks[0].priority;
-    *idmask = chain_identity_mask(c);
+    *idmask = chain_kernel_mask(c);
     *unit_weights = task_has_unit_weights(ph.tasks[0]) ? 1 : 0;
 }
 

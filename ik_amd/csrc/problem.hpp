@@ -14,10 +14,10 @@ namespace ikgpu {
 constexpr int kMaxChain = 8;
 constexpr int kMaxPostureOut = 32;  // == ikdev::kMaxPostOut: posture rows on joints outside the chains the tree kernel takes
 
-// Chain:   fixed base, ONE FrameTask whose support is a serial chain of revolute joints (shapes S, U).
+// Chain:   fixed base, ONE FrameTask whose support is a serial chain of revolute and prismatic joints (shapes S, U).
 // Tree:    free-flyer base, up to two chain FrameTasks + at most one on the base link (shape F).
 // Generic: everything else the path can express (any tree, any task list incl. AlignAxisTask rows, moving
-//          reference frames, prismatic joints): the memory-resident fallback kernel.
+//          reference frames, prismatic joints in a tree): the memory-resident fallback kernel.
 enum class KernelKind { Chain, Tree, Generic };
 
 // Packed tables of the generic kernel: one int buffer and one double buffer, with the offsets of each table.
@@ -53,9 +53,10 @@ struct GenericHost {
 };
 
 // Host copy of one serial chain (support of one task below its base), axis-folded: every joint
-// rotates about its local z.
+// rotates about its local z, or (bit j of `prismatic`) slides along it.
 struct ChainHost {
     int nj = 0;
+    int prismatic = 0;  // bit j: joint j is prismatic (Chain kind only; the tree kernels take revolute joints)
     int task = -1;  // index of the task in the (priority-ordered) task list
     int qidx[kMaxChain] = {};
     int vidx[kMaxChain] = {};
@@ -72,6 +73,7 @@ struct ChainStructure {
     uint64_t code[3] = {0, 0, 0};
     bool fits = false;
     int values = 0;   // non-structural entries: the length of the compact table before lo / hi
+    int prismatic = 0;   // ChainHost::prismatic: two chains with the same code and different masks are different structures
 };
 ChainStructure chain_structure(const ChainHost &c);
 // The compact table of that kernel: the non-structural placement values in placement order (general rotation entries
@@ -142,6 +144,9 @@ void fill_chain_args(const ProblemHost &ph, double *ref_pl12, int *qidx, int *vi
                      int *idmask, int *unit_weights);
 // Bit j set when placement j of the chain has an exactly-identity rotation; bit nj for the frame placement.
 int chain_identity_mask(const ChainHost &c);
+// ... and what fill_chain_args hands the kernels as LoopParams::idmask: that mask, and ChainHost::prismatic from bit 16 up
+// (device/chain_solver.hpp kKindShift).
+int chain_kernel_mask(const ChainHost &c);
 bool task_has_unit_weights(const ikgpu_task &t);
 // The per-problem scalars of ikdev::TreeKernelArgs<na, nb>.
 struct TreeArgsHost {

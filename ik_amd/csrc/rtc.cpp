@@ -168,10 +168,13 @@ int hot_entry(ChainJob::Kind kind, bool never) {
 // values: non-structural placement entries of the chain.  The refill kernel asks for two waves per SIMD (256 registers) unless the
 // parked table alone would take most of them.  The on-disk cache key hashes this text: one changed byte recompiles every chain that
 // a deployment has precompiled.
-std::string hot_source(int nj, const uint64_t code[3], int values) {
-    char head[160];
-    std::snprintf(head, sizeof head, "#include \"chain_hot.hpp\"\ntypedef ikdev::ChainStruct<0x%llxull, 0x%llxull, 0x%llxull> S;\n",
-                  static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]));
+// prismatic: the chain's mask of prismatic joints, the fourth argument of ChainStruct -- printed only when non-zero, so the text (and the
+// cache key) of a chain of revolute joints is what it was before there were any.
+std::string hot_source(int nj, const uint64_t code[3], int values, int prismatic) {
+    char head[192], pm[24] = "";
+    if (prismatic != 0) std::snprintf(pm, sizeof pm, ", 0x%xu", static_cast<unsigned>(prismatic));
+    std::snprintf(head, sizeof head, "#include \"chain_hot.hpp\"\ntypedef ikdev::ChainStruct<0x%llxull, 0x%llxull, 0x%llxull%s> S;\n",
+                  static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]), pm);
     const std::string n = std::to_string(nj);
     std::string src = head;
     for (const HotEntry &e : kHotEntryTable)
@@ -251,7 +254,7 @@ bool write_cached_object(const std::string &path, uint64_t key, const std::vecto
     return write_file_atomically(path, raw);
 }
 
-typedef std::tuple<int, uint64_t, uint64_t, uint64_t> ShapeKey;
+typedef std::tuple<int, uint64_t, uint64_t, uint64_t, int> ShapeKey;   // (chain length, structure code, mask of prismatic joints)
 
 struct HotCode {
     bool tried = false, ok = false;
@@ -273,7 +276,7 @@ std::string g_last_log;
 std::atomic<bool> g_in_worker{false};   // this process IS the compile worker (ikgpu_rtc_worker_compile): compile here
 
 ShapeKey key_of(const ProblemHost &ph) {
-    return ShapeKey(ph.chain.nj, ph.chain_struct.code[0], ph.chain_struct.code[1], ph.chain_struct.code[2]);
+    return ShapeKey(ph.chain.nj, ph.chain_struct.code[0], ph.chain_struct.code[1], ph.chain_struct.code[2], ph.chain_struct.prismatic);
 }
 
 struct Hdr { const char *name, *begin, *end; };
@@ -510,7 +513,7 @@ HotCode &ensure_code(Map &map, const Key &key, const char *prefix, const std::st
 
 // Compiles (or fetches) the code object of this shape.  Called WITHOUT g_mu.
 HotCode &code_for(const ProblemHost &ph) {
-    return ensure_code(g_codes, key_of(ph), "chain_hot", hot_source(ph.chain.nj, ph.chain_struct.code, ph.chain_struct.values), false);
+    return ensure_code(g_codes, key_of(ph), "chain_hot", hot_source(ph.chain.nj, ph.chain_struct.code, ph.chain_struct.values, ph.chain_struct.prismatic), false);
 }
 
 // The loaded module of this shape on the current device (a copy: the map is guarded).  Called WITHOUT g_mu.

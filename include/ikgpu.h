@@ -289,7 +289,8 @@ const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_
  *   are kept so far, and for every kept j < k there is an entry i with ikgpu_problem_support = 1 and |q_k[i] - q_j[i]| >= sep (one
  *   IEEE subtraction, fabs and a compare: reproducible bit for bit from the single solves).
  * The comparison is over plain entries: configurations that differ by a full turn of a joint are DIFFERENT configurations (they are
- * to a joint-limited robot); distance modulo 2 pi is not taken.  sep == 0 keeps every converged start, up to N.
+ * to a joint-limited robot); distance modulo 2 pi is not taken.  An entry of a prismatic joint is compared in metres with the same sep: in a
+ * support that mixes both kinds sep is one bound over radians and metres.  sep == 0 keeps every converged start, up to N.
  *   count  [B]             the number kept, at most N
  *   q_sols [N][nq x B]     each slab in the batch layout; for n < count[b], slab n holds q of the n-th kept start, bit-identical over all
  *                          nq entries to the single solve from that start (entries outside the support come from that start's own
@@ -378,7 +379,8 @@ int ikgpu_path_targets(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, 
  * failure report, ik/ik/dls.cpp:61-64,76-77) and either max_joint_step == 0 or no entry i with ikgpu_problem_support = 1 has
  *   fabs(q_n[i] - q_prev[i]) > max_joint_step,
  * q_prev being the configuration the solve started from: q0 for n = 0, slab n-1 of q_traj after that (one IEEE subtraction, fabs and a
- * compare on plain entries, as the solution set compares them: no distance modulo 2 pi).  The stop rule alone says nothing about the
+ * compare on plain entries, as the solution set compares them: no distance modulo 2 pi; an entry of a prismatic joint is compared in
+ * metres, so max_joint_step is one bound over radians and metres).  The stop rule alone says nothing about the
  * joints: with 100 iterations per waypoint a solve may reach waypoint n from waypoint n-1's configuration by swinging to another branch,
  * and a "straight-line motion" would contain a joint-space jump (the joint-jump threshold of every Cartesian-path interface).
  *   reached [B] (int32, may be NULL)  the waypoints met before the first one that was not; P * T: the whole path

@@ -32,6 +32,8 @@ KERNELS = {  # display name -> (source file, extra flags, mangled-name fragment,
     # with a run of three); keys of their own: 'dls_chain<NJ=7,full,hot-rtc>' holds the counters of the real arm7 kernel hipRTC builds
     "dls_chain<NJ=7,full,hot-rtc>|all-general stand-in": ("../../tools/hot_rtc_shapes.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "hot_rtc_shape_kernelILi7ELm8070454380540461056ELm8070454380540461056E", 1),
     "dls_chain<NJ=7,full,hot-rtc>|all-general stand-in with a run of three": ("../../tools/hot_rtc_shapes.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "hot_rtc_shape_kernelILi7ELm8070454380540461056ELm8744121078061465600E", 1),
+    # ... and a chain with a prismatic joint: a UR5 on a rail along x (joint 0 slides)
+    "dls_chain<NJ=7,full,hot-rtc>|rail UR5 stand-in (prismatic joint 0)": ("../../tools/hot_rtc_shapes.hip", ["-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"], "hot_rtc_prismatic_kernelILi7E", 1),
 }
 TRANSCENDENTAL = ("v_rcp_f64", "v_rsq_f64", "v_sqrt_f64")
 
