@@ -143,9 +143,12 @@ IKD_FN double drsqrt(double x) {
 }
 
 // sqrt(x) for x >= 0 in the normal range (0 maps to 0): x * rsqrt(x) with one correction step.
+// The floor only keeps rsqrt finite at x = 0 (s = 0 * y = 0 then) and must sit at the bottom of the normal range: with the 1e-300 it
+// had before, a normal x below it took rsqrt(1e-300) for its own and came back as 1.5 x rsqrt(1e-300) -- dsqrt(2^-1022) = 3.3e-158 for
+// 1.5e-154 (tests/test_gpu_lane_probe.py).  Results for x >= 1e-300 and x = 0 are the bits they were.
 IKD_FN double dsqrt(double x) {
 #if IKD_ON_DEVICE
-    const double y = drsqrt(dmax(x, 1e-300));
+    const double y = drsqrt(dmax(x, 0x1p-1022));
     const double s = x * y;
     return dfma(dfma(-s, s, x), 0.5 * y, s);
 #else
