@@ -896,6 +896,90 @@ def dls_multistart_batch(problem, Q0, targets, data, visitor=None, p=None, num_s
     return Q, ok, it, win, err
 
 
+class PickRule(enum.IntEnum):
+    """How dls_pick_batch ranks the starts that met the stop rule (include/ikgpu.h ikgpu_pick_rule); the smallest cost wins."""
+    DISTANCE = 0         # sum of w (q - q_ref)^2 over the task support
+    MAX_DISTANCE = 1     # max of w |q - q_ref| over the task support
+    LIMIT_MARGIN = 2     # 0.5 - the smallest relative distance to a joint limit
+    MANIPULABILITY = 3   # 1 / sqrt(det(J J^T + damping^2 I))
+
+
+def dls_pick_kernel(data, visitor=None, p=None, num_starts=8, rule=PickRule.DISTANCE):
+    """Name of what dls_pick_batch runs for these parameters: "dls_chain_pick<...>" (one launch) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_pick_kernel(data._h, C.byref(prm), num_starts, int(PickRule(rule))).decode()
+
+
+def dls_pick_batch(problem, Q0, targets, data, visitor=None, p=None, num_starts=8, rule=PickRule.DISTANCE, q_ref=None, weights=None, seed=0,
+                   starts=None, layout="soa", out=None, stream=None):
+    """Among num_starts solves per problem (dls_multistart_batch's starts), the one that met the stop rule with the smallest cost under
+    `rule`: the configuration closest to q_ref (default Q0), the one furthest from its joint limits, or the best-conditioned one
+    (TRAC-IK's Distance / Manip solve types; ik::dls is a local method: reference ik/ik/dls.cpp:10, :73).  A cost tie goes to the lowest
+    start index; when no start converged, the one with the smallest squared weighted error.  Q / success / iterations are bit-identical
+    to dls_batch from the winning start.  A chain problem with num_starts in {2, 4, ..., 64} runs one launch.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0, q_ref [nq, B], targets [ntasks, 12, B]   |   "aos": Q0, q_ref [B, nq], targets [B, ntasks, 12]
+    weights: nq non-negative floats (host), or None: ones.  Read by DISTANCE and MAX_DISTANCE only, as q_ref.
+    out: (Q, success uint8 [B], iterations int32 [B], winner int32 [B], cost float64 [B], err_sq float64 [B]) preallocated, or None.
+    Returns (Q, success, iterations, winner, cost, err_sq)."""
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    _check_starts(num_starts)
+    rule = int(PickRule(rule))
+    if len(Q0.shape) != 2 or len(targets.shape) != 3:
+        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(targets.shape)))
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
+    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
+        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
+    if q_ref is not None and tuple(q_ref.shape) != tuple(Q0.shape):
+        raise ValueError("q_ref has shape %s, expected %s" % (tuple(q_ref.shape), tuple(Q0.shape)))
+    w = None
+    if weights is not None:
+        w = [float(x) for x in weights]
+        if len(w) != model.nq:
+            raise ValueError("weights has %d entries, the model has nq = %d" % (len(w), model.nq))
+        w = (C.c_double * model.nq)(*w)
+    tensors = [Q0, targets] + ([starts] if starts is not None else []) + ([q_ref] if q_ref is not None else [])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
+        raise TypeError("dls_pick_batch needs float64 CUDA tensors")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError("dls_pick_batch needs contiguous tensors")
+    if any(t.device.index != data._device for t in tensors):
+        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
+    if out is None:
+        Q = torch.empty_like(Q0)
+        ok = torch.empty((B,), dtype=torch.uint8, device=Q0.device)
+        it = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        win = torch.empty((B,), dtype=torch.int32, device=Q0.device)
+        cost = torch.empty((B,), dtype=torch.float64, device=Q0.device)
+        err = torch.empty((B,), dtype=torch.float64, device=Q0.device)
+    else:
+        Q, ok, it, win, cost, err = out
+        _check_tensor("out[0] (Q)", Q, tuple(Q0.shape), torch.float64, data._device)
+        _check_tensor("out[1] (success)", ok, (B,), torch.uint8, data._device)
+        _check_tensor("out[2] (iterations)", it, (B,), torch.int32, data._device)
+        _check_tensor("out[3] (winner)", win, (B,), torch.int32, data._device)
+        _check_tensor("out[4] (cost)", cost, (B,), torch.float64, data._device)
+        _check_tensor("out[5] (err_sq)", err, (B,), torch.float64, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_pick_workspace_bytes(data._h, B, num_starts, C.byref(prm))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
+    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_pick_batch(data._h, B, num_starts, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
+                                      seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), rule,
+                                      q_ref.data_ptr() if q_ref is not None else None, w, Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
+                                      win.data_ptr(), cost.data_ptr(), err.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes,
+                                      C.c_void_p(s)))
+    return Q, ok, it, win, cost, err
+
+
 def dls_solutions_kernel(data, visitor=None, p=None, num_starts=8):
     """Name of what dls_solutions_batch runs for these parameters: "dls_chain_solutions<...>" (one launch) or "loop(<data.kernel>)"."""
     prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())

@@ -37,6 +37,7 @@ SYMBOLS = [
     "ikgpu_dls_track_batch", "ikgpu_dls_track_kernel",
     "ikgpu_dls_multistart_batch", "ikgpu_dls_multistart_workspace_bytes", "ikgpu_multistart_starts", "ikgpu_dls_multistart_kernel",
     "ikgpu_dls_solutions_batch", "ikgpu_dls_solutions_workspace_bytes", "ikgpu_dls_solutions_kernel",
+    "ikgpu_dls_pick_batch", "ikgpu_dls_pick_workspace_bytes", "ikgpu_dls_pick_kernel",
     "ikgpu_line_targets", "ikgpu_dls_line_batch", "ikgpu_dls_line_workspace_bytes", "ikgpu_dls_line_kernel",
     "ikgpu_dls_goalset_batch", "ikgpu_dls_goalset_workspace_bytes", "ikgpu_dls_goalset_kernel",
     "ikgpu_path_targets", "ikgpu_dls_path_batch", "ikgpu_dls_path_workspace_bytes", "ikgpu_dls_path_kernel",
@@ -160,6 +161,14 @@ def lib():
     L.ikgpu_multistart_starts.restype = C.c_int
     L.ikgpu_dls_multistart_kernel.argtypes = [vp, C.POINTER(DlsParams), i32]
     L.ikgpu_dls_multistart_kernel.restype = C.c_char_p
+    # (p, B, K, q0, starts, seed, targets, params, rule, q_ref, w, q_out, success, iters, winner, cost, err_sq, layout, workspace, bytes, stream)
+    L.ikgpu_dls_pick_batch.argtypes = [vp, i64, i32, vp, vp, C.c_uint64, vp, C.POINTER(DlsParams), i32, vp, C.POINTER(C.c_double), vp, vp, vp, vp,
+                                       vp, vp, C.c_int, vp, C.c_size_t, vp]
+    L.ikgpu_dls_pick_batch.restype = C.c_int
+    L.ikgpu_dls_pick_workspace_bytes.argtypes = [vp, i64, i32, C.POINTER(DlsParams)]
+    L.ikgpu_dls_pick_workspace_bytes.restype = C.c_size_t
+    L.ikgpu_dls_pick_kernel.argtypes = [vp, C.POINTER(DlsParams), i32, i32]
+    L.ikgpu_dls_pick_kernel.restype = C.c_char_p
     L.ikgpu_dls_solutions_batch.argtypes = [vp, i64, i32, i32, vp, vp, C.c_uint64, vp, C.POINTER(DlsParams), C.c_double, vp, vp, vp, vp, C.c_int, vp,
                                             C.c_size_t, vp]
     L.ikgpu_dls_solutions_batch.restype = C.c_int

@@ -1219,6 +1219,109 @@ int ikgpu_dls_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, con
     });
 }
 
+}  // extern "C"
+
+namespace {
+
+static_assert(ikdev::kPickMaxChain >= ikgpu::kMaxChain, "PickArgs::w holds a weight per chain joint");
+
+bool pick_rule_known(int32_t rule) { return rule >= IKGPU_PICK_DISTANCE && rule <= IKGPU_PICK_MANIPULABILITY; }
+
+// The workspace of the pick definition run as a loop: the multi-start loop's (start_workspace with the error), then the start's cost
+// [B], its dense Jacobian [M x nv x B] and Gram matrix [M x M x B] (the MANIPULABILITY rule) and the weights [nq].
+struct PickWorkspace {
+    size_t cost, J, G, w, total;
+};
+PickWorkspace pick_workspace(const ikgpu_problem *p, int64_t B) {
+    size_t end = start_workspace(p, B, /*with_error=*/true).total;
+    auto take = [&](size_t n) { const size_t at = end; end += (n + 255) / 256 * 256; return at; };
+    const size_t b = static_cast<size_t>(B), M = static_cast<size_t>(p->host.rows);
+    PickWorkspace w{};
+    w.cost = take(8 * b);
+    w.J = take(8 * M * static_cast<size_t>(p->host.nv) * b);
+    w.G = take(8 * M * M * b);
+    w.w = take(8 * static_cast<size_t>(p->host.nq));
+    w.total = end;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *ikgpu_dls_pick_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K, int32_t rule) {
+    if (!p || !params || !pick_rule_known(rule)) return "";
+    thread_local std::string name;
+    name = variant_kernel_name(p, multistart_fused_log2(p, params, K) >= 0, "_pick");
+    return name.c_str();
+}
+
+size_t ikgpu_dls_pick_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, const ikgpu_dls_params *params) {
+    if (!p || !params || B <= 0 || K < 1 || K > 64 || multistart_fused_log2(p, params, K) >= 0) return 0;
+    return pick_workspace(p, B).total;
+}
+
+int ikgpu_dls_pick_batch(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, const double *starts, uint64_t seed,
+                         const double *targets, const ikgpu_dls_params *params, int32_t rule, const double *q_ref, const double *w,
+                         double *q_out, uint8_t *success, int32_t *iters, int32_t *winner, double *cost, double *err_sq, int layout,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_starts(K)) return rc;
+    if (int rc = refuse_if(!pick_rule_known(rule), "unknown pick rule (ikgpu_pick_rule)")) return rc;
+    if (int rc = check_layout(layout)) return rc;
+    if (int rc = check_params(params)) return rc;
+    if (params->stop_sq_tol < 0.0 && !ikgpu::visitor_extended(*params))
+        return fail(IKGPU_ERR_INVALID, "the never-stop visitor has no converged start: a pick needs a stop rule (stop_sq_tol >= 0)");
+    if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
+    if (!q0 || !targets || !q_out) return null_argument();
+    if (int rc = check_launch_size(B, K)) return rc;
+    if (w)
+        for (int i = 0; i < p->host.nq; ++i)
+            if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(IKGPU_ERR_INVALID, "w[" + std::to_string(i) + "] must be finite and not negative");
+    const int log2K = multistart_fused_log2(p, params, K);
+    // (the loop's workspace is refused here, before the device is selected; run_starts checks its own part again)
+    if (log2K < 0 && (!workspace || workspace_bytes < pick_workspace(p, B).total))
+        return fail(IKGPU_ERR_INVALID, "pick workspace too small: " + std::to_string(workspace ? workspace_bytes : 0) + " bytes given, " +
+                                           std::to_string(pick_workspace(p, B).total) + " needed (ikgpu_dls_pick_workspace_bytes)");
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        if (log2K >= 0) {
+            const ikgpu::BatchIO io{B, q0, targets, q_out, success, iters, layout};
+            ikgpu::ChainJob job{};
+            job.kind = ikgpu::ChainJob::Pick;
+            job.pick.ms = ikdev::MultistartArgs{starts, p->dev.draw, seed, winner, err_sq, log2K};
+            job.pick.q_ref = q_ref;
+            job.pick.cost = cost;
+            job.pick.rule = rule;
+            for (int j = 0; j < ikdev::kPickMaxChain; ++j)   // (the support of a chain problem is its chain: w by chain joint)
+                job.pick.w[j] = (w && j < p->host.chain.nj) ? w[p->host.chain.qidx[j]] : 1.0;
+            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the pick DLS kernel");
+        }
+        // every other case: the definition itself, each start's cost computed and the start merged into the caller's outputs
+        const PickWorkspace pw = pick_workspace(p, B);
+        char *ws = static_cast<char *>(workspace);
+        double *c_k = reinterpret_cast<double *>(ws + pw.cost), *J = reinterpret_cast<double *>(ws + pw.J), *G = reinterpret_cast<double *>(ws + pw.G);
+        double *w_dev = nullptr;
+        const bool weighted = w && (rule == IKGPU_PICK_DISTANCE || rule == IKGPU_PICK_MAX_DISTANCE);
+        if (weighted) {   // (w is pageable host memory: the copy has left it when the call returns)
+            w_dev = reinterpret_cast<double *>(ws + pw.w);
+            if (const int rc = launched(hipMemcpyAsync(w_dev, w, sizeof(double) * static_cast<size_t>(p->host.nq), hipMemcpyHostToDevice, st), "copying the pick weights"))
+                return rc;
+        }
+        const bool manip = rule == IKGPU_PICK_MANIPULABILITY;
+        const StartsCall c{B, K, q0, starts, seed, targets, params, layout, workspace, start_workspace(p, B, true).total};
+        return run_starts(p, c, "pick", "ikgpu_dls_pick_workspace_bytes", /*with_error=*/true, st,
+                          [&](int k, double *q, uint8_t *ok, int32_t *it, double *e, unsigned long long *key) {
+                              if (const int rc = dispatch_eval(p, B, q, targets, e, manip ? J : nullptr, layout, st)) return rc;
+                              const ikgpu::PickCost pc{B, p->host.nq, p->host.nv, p->host.rows, layout, rule, params->damping * params->damping,
+                                                       p->dev.q_in_chain, p->dev.lower, p->dev.upper, q, q_ref ? q_ref : q0, w_dev, J, G, c_k};
+                              if (const int rc = launched(ikgpu::launch_pick_cost(pc, st), "launching the pick cost")) return rc;
+                              const ikgpu::PickMerge m{ikgpu::MultistartMerge{B, p->host.nq, p->host.rows, layout, k, q, e, ok, it, key, q_out, success, iters, winner, err_sq},
+                                                       c_k, cost};
+                              return launched(ikgpu::launch_pick_merge(m, st), "launching the pick merge");
+                          });
+    });
+}
+
 const char *ikgpu_dls_solutions_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
     if (!p || !params) return "";
     thread_local std::string name;

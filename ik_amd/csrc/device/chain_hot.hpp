@@ -844,6 +844,43 @@ IKD_FN void hot_multistart_body(const ChainKernelArgs<NJ> &a, const MultistartAr
                          [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
 }
 
+// K starts per problem, the converged one with the smallest cost stored -- dls_chain_pick_body (chain_kernel_body.hpp: the definition,
+// the lane mapping, the pieces) with the hot program: hot_multistart_lane's statements, then the cost at the result; the trailing
+// evaluation's Jacobian columns and hot_gram are live under the MANIPULABILITY rule alone.  Always under a stop rule.
+template <int NJ, class S, class Tab, class AnyFn>
+IKD_FN void hot_pick_lane(const ChainKernelArgs<NJ> &a, const PickArgs &pk, const Tab &t, int64_t b, int k, double (&q)[NJ], bool &success,
+                          int &iters, double &err_sq, double &cost, AnyFn any_active) {
+    const auto lut_stage = hot_lut_issue(t);   // (hot_chain_body)
+    multistart_load(a, pk.ms, b, k, q);
+    double oMt[12];
+    load_target(a, b, oMt);
+    hot_lut_commit(t, lut_stage);
+    hot_dls<NJ, S, false>(t, a.prm, q, oMt, iters, success, any_active);
+    double e[6], col[NJ][6], oM0[12];
+    hot_fold_base<S>(t, oMt, oM0);   // (hot_dls's own fold again: the same values, and P_0 stays out of the loop's live registers)
+    hot_evaluate<NJ, S, true>(t, q, oM0, e, col);
+    err_sq = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) err_sq = dfma(e[r], e[r], err_sq);
+    cost = pick_chain_cost<6>(a, pk, b, q, [&](double (&G)[36]) { hot_gram<NJ, S>(col, a.prm.lam2, G); });
+}
+
+template <int NJ, class S, class Tab, class AnyFn, class Exchange>
+IKD_FN void hot_pick_body(const ChainKernelArgs<NJ> &a, const PickArgs &pk, const Tab &t, int64_t gid, AnyFn any_active, Exchange exchange) {
+    const int64_t prob = gid >> pk.ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << pk.ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq, cost;
+    bool success;
+    int iters;
+    hot_pick_lane<NJ, S>(a, pk, t, b, k, q, success, iters, err_sq, cost, any_active);
+    const int win = multistart_select(pk.ms.log2K, pick_key(success, cost, err_sq), k, exchange);
+    if (valid && win == k)
+        pick_store(a, pk, b, k, q, success, iters, err_sq, cost,
+                   [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
+}
+
 // G goals and K starts per problem, the best candidate stored -- dls_chain_goalset_body (chain_kernel_body.hpp: the definition, the lane
 // mapping, the pieces) with the hot program: hot_multistart_lane with the target taken from slab g of the goals.
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
@@ -991,6 +1028,14 @@ __device__ __forceinline__ void hot_multistart_entry(const ChainKernelArgs<NJ> &
     IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_multistart_body<NJ, S, NEVERSTOP>(a, ms, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
+}
+
+template <int NJ, class S>
+__device__ __forceinline__ void hot_pick_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const PickArgs &pk) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    IKD_HOT_LUT_DECLARE(tv);
+    hot_park_table<NJ, S>(t, tv);
+    hot_pick_body<NJ, S>(a, pk, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
 }
 
 template <int NJ, class S, bool NEVERSTOP>

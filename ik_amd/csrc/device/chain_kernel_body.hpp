@@ -10,6 +10,7 @@
 #include "goalset.hpp"
 #include "line.hpp"
 #include "multistart.hpp"
+#include "pick.hpp"
 #include "solutions.hpp"
 
 namespace ikdev {
@@ -428,6 +429,97 @@ IKD_FN void dls_chain_multistart_body(const ChainKernelArgs<NJ> &a, const Multis
     const int win = multistart_select(ms.log2K, multistart_key(success, err_sq), k, exchange);
     if (valid && win == k)
         multistart_store(a, ms, b, k, q, success, iters, err_sq, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
+}
+
+// ---- pick: K starts per problem in one launch, the converged one with the smallest cost stored (include/ikgpu.h ikgpu_dls_pick_batch) ----
+// Defined through the K single solves of the multi-start call (the same starts, the same lane mapping, the same error) and a cost
+// at each result (device/pick.hpp): the key orders (met the stop rule, cost | error, k).  The multi-start pieces again; the trailing
+// evaluation's Jacobian is read by the MANIPULABILITY rule alone.  Always under a stop rule (without one no start converges and the
+// rule could never act: the entry point refuses the call).
+
+// The cost of a chain problem's start from its chain entries q: the support of a chain problem is its chain.  gram(G) fills the lower
+// triangle of J J^T + damping^2 I at q (the build's own Gram matrix of the trailing evaluation).  pk.rule is wave-uniform.
+template <int M, int NJ, class Gram>
+IKD_FN double pick_chain_cost(const ChainKernelArgs<NJ> &a, const PickArgs &pk, int64_t b, const double (&q)[NJ], Gram gram) {
+    static_assert(NJ <= kPickMaxChain, "PickArgs::w is too short for this chain");
+    if (pk.rule == PICK_MANIPULABILITY) {
+        double G[M * M];
+        gram(G);
+        return pick_manipulability_cost(pick_ldlt_det<M>(G));
+    }
+    if (pk.rule == PICK_LIMIT_MARGIN) {
+        double margin = 0.5;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) margin = pick_margin_step(margin, q[j], a.lower[a.qidx[j]], a.upper[a.qidx[j]]);
+        return pick_margin_cost(margin);
+    }
+    const ChainStrides st = chain_strides(a);
+    const double *ref = pk.q_ref ? pk.q_ref : a.q0;
+    double r[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) r[j] = ref[at(st.elem, st.q_prob, a.qidx[j], b)];
+    double cost = 0.0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        cost = pk.rule == PICK_DISTANCE ? pick_distance_step(cost, pk.w[j], q[j], r[j]) : pick_max_distance_step(cost, pk.w[j], q[j], r[j]);
+    return cost;
+}
+
+// One start: the multi-start lane (dls_chain_multistart_lane: the same statements), then the cost at its result.
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN void dls_chain_pick_lane(const ChainKernelArgs<NJ> &a, const PickArgs &pk, const Desc &d, int64_t b, int k, double (&q)[NJ], bool &success,
+                                int &iters, double &err_sq, double &cost, AnyFn any_active) {
+    constexpr int M = TaskDim<KT>::value;
+    multistart_load(a, pk.ms, b, k, q);
+    double oMt[12];
+    load_target(a, b, oMt);
+    chain_dls<NJ, KT, SMASK>(d, a.prm, q, oMt, iters, success, any_active);
+    double e[M], col[NJ][M], Rf[9], pf[3];
+    chain_evaluate<NJ, KT, SMASK>(d, q, oMt, a.prm.idmask, a.prm.unit_weights != 0, e, col, Rf, pf);
+    err_sq = 0.0;
+#pragma unroll
+    for (int r = 0; r < M; ++r) err_sq = dfma(e[r], e[r], err_sq);
+    // MANIPULABILITY is defined on the Jacobian ikgpu_evaluate_batch returns at q: evaluated once more in the stage kernels' own form
+    // (eval_chain_body: accurate sin / cos, run-time mask and weights), under that rule alone.  The loop's form differs from it by rounding
+    // that a Position or Orientation task amplifies without bound -- its unconstrained rotation error may lie near pi, where the
+    // coefficients of log6's Jacobian cancel -- and the cost would then depend on the build.
+    cost = pick_chain_cost<M>(a, pk, b, q, [&](double (&G)[M * M]) {   // (chain_iteration's Gram matrix)
+        constexpr int kStage = ReadsKinds<SMASK>::value ? kSpecRuntimeKinds : -1;
+        double es[M], cs[NJ][M], Rs[9], ps[3];
+        chain_evaluate<NJ, KT, kStage>(d, q, oMt, a.prm.idmask, a.prm.unit_weights != 0, es, cs, Rs, ps);
+#pragma unroll
+        for (int r = 0; r < M; ++r)
+#pragma unroll
+            for (int c = 0; c <= r; ++c) {
+                double s = (r == c) ? a.prm.lam2 : 0.0;
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) s = dfma(cs[j][r], cs[j][c], s);
+                G[r * M + c] = s;
+            }
+    });
+}
+
+// The winning lane's stores: multistart_store and the winner's cost.
+template <int NJ, class Pass>
+IKD_FN void pick_store(const ChainKernelArgs<NJ> &a, const PickArgs &pk, int64_t b, int k, const double (&q)[NJ], bool success, int iters,
+                       double err_sq, double cost, Pass pass) {
+    multistart_store(a, pk.ms, b, k, q, success, iters, err_sq, pass);
+    if (pk.cost) pk.cost[b] = cost;
+}
+
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn, class Exchange>
+IKD_FN void dls_chain_pick_body(const ChainKernelArgs<NJ> &a, const PickArgs &pk, const Desc &d, int64_t gid, AnyFn any_active, Exchange exchange) {
+    const int64_t prob = gid >> pk.ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << pk.ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq, cost;
+    bool success;
+    int iters;
+    dls_chain_pick_lane<NJ, KT, SMASK>(a, pk, d, b, k, q, success, iters, err_sq, cost, any_active);
+    const int win = multistart_select(pk.ms.log2K, pick_key(success, cost, err_sq), k, exchange);
+    if (valid && win == k)
+        pick_store(a, pk, b, k, q, success, iters, err_sq, cost, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
 }
 
 // ---- goal set: G alternative goals and K starts per problem in one launch, the best candidate stored (include/ikgpu.h

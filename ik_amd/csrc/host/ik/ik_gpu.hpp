@@ -805,6 +805,33 @@ inline void dls_multistart_device(InverseKinematicsProblem &problem, std::int64_
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// Among K starts per problem on DEVICE buffers (dls_multistart_device's starts), the one that met the stop rule with the smallest cost
+// under `rule`: the configuration closest to q_ref (null: Q0), the one furthest from its joint limits, or the best-conditioned one
+// (include/ikgpu.h ikgpu_dls_pick_batch; ik::dls is a local method: ik/ik/dls.cpp:10, :73).  A tie goes to the lowest index; when no start
+// converged, the smallest squared weighted error wins.  Q / success / iterations are bit-identical to dls_batch_device from the winning
+// start.  weights: HOST [nq] or null (ones).  success / iterations / winner / cost / err_sq [B] may be null.  workspace: device memory of
+// pick_workspace_bytes() bytes (0 for a chain problem with K in {2, 4, .., 64}: one launch).  Asynchronous on `stream`.
+enum class pick_rule : int { distance = IKGPU_PICK_DISTANCE, max_distance = IKGPU_PICK_MAX_DISTANCE, limit_margin = IKGPU_PICK_LIMIT_MARGIN,
+                             manipulability = IKGPU_PICK_MANIPULABILITY };
+inline std::size_t pick_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, int K, dls_data &data,
+                                        const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                        const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_pick_workspace_bytes(data.handle(), B, K, &prm);
+}
+inline void dls_pick_batch(InverseKinematicsProblem &problem, std::int64_t B, int K, const number_t *Q0, const number_t *starts, std::uint64_t seed,
+                           const number_t *targets, dls_data &data, pick_rule rule, const number_t *q_ref, const number_t *weights, number_t *Q,
+                           std::uint8_t *success, std::int32_t *iterations, std::int32_t *winner, number_t *cost, number_t *err_sq, void *workspace,
+                           std::size_t workspace_bytes, void *stream, const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                           const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_pick_batch(data.handle(), B, K, Q0, starts, seed, targets, &prm, static_cast<std::int32_t>(rule), q_ref, weights, Q, success,
+                             iterations, winner, cost, err_sq, IKGPU_SOA, workspace, workspace_bytes, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // The distinct solutions among K starts per problem on DEVICE buffers (the starts are dls_multistart_device's; ik::dls is a local method:
 // ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 stays inert).  In increasing start index a start is kept when it met the stop rule, fewer than N
 // are kept, and some entry of the task support differs by `separation` or more from every start kept before it.  count [B]; for

@@ -252,6 +252,15 @@ __global__ __launch_bounds__(kBlock) void dls_chain_multistart_kernel(const Chai
     ikdev::dls_chain_multistart_body<NJ, KT, SMASK>(a, ms, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
 }
 
+// K starts per problem in one launch, the converged one with the smallest cost stored (device/chain_kernel_body.hpp dls_chain_pick_body):
+// the general build's pick kernel, one instantiation for the four rules.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_pick_kernel(const ChainKernelArgs<NJ> a, const ikdev::PickArgs pk) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    ikdev::dls_chain_pick_body<NJ, KT, SMASK>(a, pk, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
+}
+
 // K starts per problem in one launch, the distinct converged ones stored (device/chain_kernel_body.hpp dls_chain_solutions_body): the
 // general build's solution-set kernel.
 template <int NJ, int KT, int SMASK>
@@ -309,6 +318,68 @@ __global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m)
     if (m.iters_out) m.iters_out[b] = m.iters[b];
     if (m.winner) m.winner[b] = m.k;
     if (m.err_sq) m.err_sq[b] = err;
+}
+
+// The cost of one start's result (device/pick.hpp), one thread per problem: the support entries in increasing index; MANIPULABILITY
+// forms G = J J^T + lam2 I from the dense J and eliminates it in place (pick_ldlt_det's steps over memory, any M).
+__global__ __launch_bounds__(256) void pick_cost_kernel(const PickCost c) {
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= c.B) return;
+    double cost = 0.0;
+    if (c.rule == ikdev::PICK_MANIPULABILITY) {
+        const int M = c.M;
+        auto g = [&](int r, int s) -> double & { return c.G[static_cast<int64_t>(r * M + s) * c.B + b]; };
+        for (int r = 0; r < M; ++r)
+            for (int s = 0; s <= r; ++s) {
+                double acc = (r == s) ? c.lam2 : 0.0;
+                for (int v = 0; v < c.nv; ++v)
+                    acc = ikdev::dfma(c.J[ikdev::at(c.layout, c.B, M * c.nv, r * c.nv + v, b)], c.J[ikdev::at(c.layout, c.B, M * c.nv, s * c.nv + v, b)], acc);
+                g(r, s) = acc;
+            }
+        double det = 1.0;
+        for (int k = 0; k < M; ++k) {
+            det = det * g(k, k);
+            const double inv = ikdev::drcp(g(k, k));
+            for (int i = k + 1; i < M; ++i) {
+                const double l = g(i, k) * inv;
+                for (int j = k + 1; j <= i; ++j) g(i, j) = ikdev::dfma(-l, g(j, k), g(i, j));
+            }
+        }
+        cost = ikdev::pick_manipulability_cost(det);
+    } else if (c.rule == ikdev::PICK_LIMIT_MARGIN) {
+        double margin = 0.5;
+        for (int i = 0; i < c.nq; ++i)
+            if (c.support[i]) margin = ikdev::pick_margin_step(margin, c.q[ikdev::at(c.layout, c.B, c.nq, i, b)], c.lower[i], c.upper[i]);
+        cost = ikdev::pick_margin_cost(margin);
+    } else {
+        for (int i = 0; i < c.nq; ++i) {
+            if (!c.support[i]) continue;
+            const int64_t at = ikdev::at(c.layout, c.B, c.nq, i, b);
+            const double w = c.w ? c.w[i] : 1.0;
+            cost = c.rule == ikdev::PICK_DISTANCE ? ikdev::pick_distance_step(cost, w, c.q[at], c.q_ref[at]) : ikdev::pick_max_distance_step(cost, w, c.q[at], c.q_ref[at]);
+        }
+    }
+    c.cost[b] = cost;
+}
+
+__global__ __launch_bounds__(256) void pick_merge(const PickMerge p) {
+    const MultistartMerge &m = p.m;
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= m.B) return;
+    double err = 0.0;
+    for (int r = 0; r < m.M; ++r) {
+        const double e = m.e[ikdev::at(m.layout, m.B, m.M, r, b)];
+        err = ikdev::dfma(e, e, err);
+    }
+    const unsigned long long key = ikdev::pick_key(m.success[b] != 0, p.cost[b], err);
+    if (m.k > 0 && !(key < m.key[b])) return;   // (a tie keeps the lower index)
+    m.key[b] = key;
+    for (int i = 0; i < m.nq; ++i) m.q_out[ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
+    if (m.success_out) m.success_out[b] = m.success[b];
+    if (m.iters_out) m.iters_out[b] = m.iters[b];
+    if (m.winner) m.winner[b] = m.k;
+    if (m.err_sq) m.err_sq[b] = err;
+    if (p.cost_out) p.cost_out[b] = p.cost[b];
 }
 
 __global__ __launch_bounds__(256) void goalset_reachable_kernel(int64_t B, bool first, const uint8_t *success, uint8_t *reachable) {
@@ -434,8 +505,10 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         constexpr int SM = decltype(smask)::value;
         if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
         const dim3 grid = grid_for(job.lanes(io.B));
-        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line || job.kind == ChainJob::Path) && prm.stop_sq_tol < 0.0) return hipErrorInvalidValue;
-        if (job.kind == ChainJob::Path) hipLaunchKernelGGL((dls_chain_path_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.path);
+        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line || job.kind == ChainJob::Path || job.kind == ChainJob::Pick) && prm.stop_sq_tol < 0.0)
+            return hipErrorInvalidValue;
+        if (job.kind == ChainJob::Pick) hipLaunchKernelGGL((dls_chain_pick_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.pick);
+        else if (job.kind == ChainJob::Path) hipLaunchKernelGGL((dls_chain_path_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.path);
         else if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
         else if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
         else if (job.kind == ChainJob::Solutions) hipLaunchKernelGGL((dls_chain_solutions_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.sol);
@@ -681,6 +754,16 @@ hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, i
 
 hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream) {
     hipLaunchKernelGGL(multistart_merge, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_pick_cost(const PickCost &c, hipStream_t stream) {
+    hipLaunchKernelGGL(pick_cost_kernel, dim3(static_cast<unsigned>((c.B + 255) / 256)), dim3(256), 0, stream, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_pick_merge(const PickMerge &m, hipStream_t stream) {
+    hipLaunchKernelGGL(pick_merge, dim3(static_cast<unsigned>((m.m.B + 255) / 256)), dim3(256), 0, stream, m);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include "device/goalset.hpp"
 #include "device/line.hpp"
 #include "device/multistart.hpp"
+#include "device/pick.hpp"
 #include "device/solutions.hpp"
 #include "problem.hpp"
 
@@ -90,18 +91,21 @@ struct BatchIO {
 //               joint-step rule (ikgpu_dls_path_batch; dls_chain_path_body, hot_path_body): `io.targets` holds the P slabs of vias, the
 //               waypoints are formed on the lane (device/line.hpp), a problem stops at its first waypoint that was not met and
 //               path.reached counts the ones before it.  Needs a stop rule, as Line.
-// Track, Multistart, Solutions, Line, Goalset and Path are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
+//   Pick:       the Multistart lanes (pick.ms), the start that met the stop rule with the smallest cost stored (ikgpu_dls_pick_batch;
+//               dls_chain_pick_body, hot_pick_body).  Needs a stop rule, as Solutions.
+// Track, Multistart, Solutions, Line, Goalset, Path and Pick are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
 // capturable.
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset, Path } kind = Solve;
+    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset, Path, Pick } kind = Solve;
     int T = 0;                     // Track: the number of waypoints
     ikdev::MultistartArgs ms{};    // Multistart
     ikdev::SolutionsArgs sol{};    // Solutions
     ikdev::LineArgs line{};        // Line
     ikdev::GoalsetArgs goal{};     // Goalset
     ikdev::PathArgs path{};        // Path
+    ikdev::PickArgs pick{};        // Pick
     int64_t lanes(int64_t B) const {   // one lane per problem, per start, or per (goal, start)
-        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : B;
+        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : kind == Pick ? B << pick.ms.log2K : B;
     }
 };
 
@@ -159,6 +163,27 @@ struct MultistartMerge {
     double *err_sq;
 };
 hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream);
+// One step of the pick definition run as a loop (ikgpu_dls_pick_batch), in two launches.  launch_pick_cost: cost[b] of start k's result q
+// under `rule` (device/pick.hpp) over the support entries in increasing index; MANIPULABILITY reads the dense J [M x nv x B]
+// ikgpu_evaluate_batch wrote at q and eliminates G [M x M x B] in place.  launch_pick_merge: launch_multistart_merge under pick_key.
+struct PickCost {
+    int64_t B;
+    int nq, nv, M, layout, rule;
+    double lam2;
+    const uint8_t *support;         // [nq] (DeviceTables::q_in_chain)
+    const double *lower, *upper;    // [nq]
+    const double *q, *q_ref, *w;    // [nq x B], [nq x B], [nq] or null: ones
+    const double *J;                // [M x nv x B]   (MANIPULABILITY)
+    double *G;                      // [M x M x B]    (MANIPULABILITY)
+    double *cost;                   // [B]
+};
+hipError_t launch_pick_cost(const PickCost &c, hipStream_t stream);
+struct PickMerge {
+    MultistartMerge m;
+    const double *cost;             // [B] start k's cost
+    double *cost_out;               // [B] or null
+};
+hipError_t launch_pick_merge(const PickMerge &m, hipStream_t stream);
 // One step of the goal-set definition run as a loop: reachable[b] = (first ? 0 : reachable[b]) | success[b], over the starts of one goal.
 hipError_t launch_goalset_reachable(int64_t B, bool first, const uint8_t *success, uint8_t *reachable, hipStream_t stream);
 // ... and its last: the winning candidate j = winner[b] (which may be `goal` or `start` itself) into goal[b] = j / K, start[b] = j % K;

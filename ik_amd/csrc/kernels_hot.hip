@@ -56,6 +56,14 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_multistart_kernel(const 
     ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms);
 }
 
+// K starts per problem in one launch, the converged one with the smallest cost stored (device/chain_hot.hpp hot_pick_body; include/ikgpu.h
+// ikgpu_dls_pick_batch): the multi-start kernel's lane mapping, one instantiation for the four rules.  Stop rule only; lock-step; no LDS
+// beyond the sin / cos table, no queue slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_pick_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::PickArgs pk) {
+    ikdev::hot_pick_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pk);
+}
+
 // G goals and K starts per problem in one launch, the best candidate stored (device/chain_hot.hpp hot_goalset_body; include/ikgpu.h
 // ikgpu_dls_goalset_batch): lane gid serves problem gid / (G K) with goal (gid / K) % G and start gid % K.  Lock-step; no LDS, no queue
 // slot, no allocation.
@@ -147,6 +155,9 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
         } else if (job.kind == ChainJob::Solutions) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (no start converges without a stop rule: the entry point refuses the call)
             else hipLaunchKernelGGL((dls_chain_hot_solutions_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.sol);
+        } else if (job.kind == ChainJob::Pick) {
+            if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
+            else hipLaunchKernelGGL((dls_chain_hot_pick_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.pick);
         } else if (job.kind == ChainJob::Line) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (nothing is ever reached without a stop rule: refused likewise)
             else hipLaunchKernelGGL((dls_chain_hot_line_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.line);

@@ -61,6 +61,7 @@ IKGPU_EMBED(ikgpu_src_chain_solver, "device/chain_solver.hpp")
 IKGPU_EMBED(ikgpu_src_goalset, "device/goalset.hpp")
 IKGPU_EMBED(ikgpu_src_line, "device/line.hpp")
 IKGPU_EMBED(ikgpu_src_multistart, "device/multistart.hpp")
+IKGPU_EMBED(ikgpu_src_pick, "device/pick.hpp")
 IKGPU_EMBED(ikgpu_src_solutions, "device/solutions.hpp")
 IKGPU_EMBED(ikgpu_src_chain_kernel_body, "device/chain_kernel_body.hpp")
 IKGPU_EMBED(ikgpu_src_chain_hot, "device/chain_hot.hpp")
@@ -130,7 +131,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 //       ikdev::<entry><NJ, S<flag>>(a, t<args>);
 //   }
 enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotSolutionsStop, kHotLineStop,
-       kHotGoalsetNever, kHotGoalsetStop, kHotPathStop, kHotEntries };
+       kHotGoalsetNever, kHotGoalsetStop, kHotPathStop, kHotPickStop, kHotEntries };
 struct HotEntry {
     const char *name, *params, *entry, *flag, *args;
     bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
@@ -154,12 +155,15 @@ const HotEntry kHotEntryTable[kHotEntries] = {
     {"ikgpu_hot_goalset_stop", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", false", ", ga", false},
     // a Cartesian path through P vias per problem with the joint-step rule (ikgpu_dls_path_batch): a stop rule always, so one entry
     {"ikgpu_hot_path_stop", ", const ikdev::PathArgs pa", "hot_path_entry", "", ", pa", false},
+    // K starts per problem in one launch, the converged one with the smallest cost stored (ikgpu_dls_pick_batch): a stop rule always, so one entry
+    {"ikgpu_hot_pick_stop", ", const ikdev::PickArgs pk", "hot_pick_entry", "", ", pk", false},
 };
 // The row of a job, or -1: a solution-set, line or path job has no never-stop entry.
 int hot_entry(ChainJob::Kind kind, bool never) {
     if (kind == ChainJob::Solutions) return never ? -1 : kHotSolutionsStop;
     if (kind == ChainJob::Line) return never ? -1 : kHotLineStop;
     if (kind == ChainJob::Path) return never ? -1 : kHotPathStop;
+    if (kind == ChainJob::Pick) return never ? -1 : kHotPickStop;
     if (kind == ChainJob::Goalset) return never ? kHotGoalsetNever : kHotGoalsetStop;
     static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
     return first[kind] + (never ? 0 : 1);
@@ -286,6 +290,7 @@ const Hdr kHeaders[] = {{"sincos_lut_table.hpp", ikgpu_src_sincos_lut_table, ikg
                         {"goalset.hpp", ikgpu_src_goalset, ikgpu_src_goalset_end},
                         {"line.hpp", ikgpu_src_line, ikgpu_src_line_end},
                         {"multistart.hpp", ikgpu_src_multistart, ikgpu_src_multistart_end},
+                        {"pick.hpp", ikgpu_src_pick, ikgpu_src_pick_end},
                         {"solutions.hpp", ikgpu_src_solutions, ikgpu_src_solutions_end},
                         {"chain_kernel_body.hpp", ikgpu_src_chain_kernel_body, ikgpu_src_chain_kernel_body_end},
                         {"chain_hot.hpp", ikgpu_src_chain_hot, ikgpu_src_chain_hot_end},
@@ -571,17 +576,18 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
             ikdev::LineArgs la;
             ikdev::GoalsetArgs ga;
             ikdev::PathArgs pa;
+            ikdev::PickArgs pk;
         } tail;
     } args{};
     constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
     static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8 &&
                       alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8 && alignof(ikdev::GoalsetArgs) == 8 &&
-                      alignof(ikdev::PathArgs) == 8, "argument layout");
+                      alignof(ikdev::PathArgs) == 8 && alignof(ikdev::PickArgs) == 8, "argument layout");
     constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
                      kBytesTrack = offsetof(Args, tail.T) + sizeof(int),
                      kBytesMultistart = offsetof(Args, tail) + sizeof(ikdev::MultistartArgs), kBytesSolutions = offsetof(Args, tail) + sizeof(ikdev::SolutionsArgs),
                      kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs), kBytesGoalset = offsetof(Args, tail) + sizeof(ikdev::GoalsetArgs),
-                     kBytesPath = offsetof(Args, tail) + sizeof(ikdev::PathArgs);
+                     kBytesPath = offsetof(Args, tail) + sizeof(ikdev::PathArgs), kBytesPick = offsetof(Args, tail) + sizeof(ikdev::PickArgs);
     static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
     static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
     static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
@@ -590,6 +596,7 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     static_assert(kBytesLine == kHead + sizeof(ikdev::LineArgs), "line: the whole of (a, t, la)");
     static_assert(kBytesGoalset == kHead + sizeof(ikdev::GoalsetArgs), "goal set: the whole of (a, t, ga)");
     static_assert(kBytesPath == kHead + sizeof(ikdev::PathArgs), "path: the whole of (a, t, pa)");
+    static_assert(kBytesPick == kHead + sizeof(ikdev::PickArgs), "pick: the whole of (a, t, pk)");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
     fill_chain_kernel_args(a, ph, dt);
     fill_solve_args(a, io, prm);
@@ -615,6 +622,10 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     if (job.kind == ChainJob::Path) {
         args.tail.pa = job.path;
         return launch(entry, waves, kBytesPath);
+    }
+    if (job.kind == ChainJob::Pick) {
+        args.tail.pk = job.pick;
+        return launch(entry, waves, kBytesPick);
     }
     if (job.kind == ChainJob::Goalset) {
         args.tail.ga = job.goal;

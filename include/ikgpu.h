@@ -277,6 +277,50 @@ int ikgpu_multistart_starts(const ikgpu_problem *p, int64_t B, int32_t K, const 
  * ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27 -- and has no such choice.) */
 const char *ikgpu_dls_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K);
 
+/* ---- pick: among K starts per problem, the one that met the stop rule with the smallest COST.  The multi-start call answers "did any
+ * start reach the target" with the lowest-index one; a caller who runs several starts usually wants a particular solution -- the
+ * configuration closest to where the arm is now, the one furthest from its joint limits, the best-conditioned one (TRAC-IK's Distance,
+ * Manip1 and Manip2 solve types; the reference itself only plans its restarts: ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27).  1 <= K <= 64.
+ * DEFINED through K calls of ikgpu_dls_solve_batch exactly as ikgpu_dls_multistart_batch is: the starts, the draw,
+ * r_k = (q_k, success_k, iters_k) and err_k are word for word those of that call;
+ *   the winner is the k with the smallest key (success_k ? 0 : 1, success_k ? cost_k : err_k, k): among the starts that met the stop
+ *   rule the smallest cost, a tie going to the lowest index; when none did, the smallest error, as multi-start.  A non-finite cost or
+ *   error ranks as +infinity.
+ * q_out [nq x B], success [B], iters [B] are r_winner bit for bit, over all nq entries; winner [B] is the start's index, cost [B] is
+ * cost_winner (also when no start converged) and err_sq [B] is err_winner.  success, iters, winner, cost and err_sq may each be NULL.
+ * The costs, all non-negative, over the entries i with ikgpu_problem_support = 1 ("support"), accumulated in increasing i (a chain
+ * kernel: along the chain):
+ *   IKGPU_PICK_DISTANCE        sum_i w[i] (q_k[i] - q_ref[i])^2
+ *   IKGPU_PICK_MAX_DISTANCE    max_i w[i] |q_k[i] - q_ref[i]|
+ *   IKGPU_PICK_LIMIT_MARGIN    0.5 - min_i min(q_k[i] - lower[i], upper[i] - q_k[i]) / (upper[i] - lower[i]), the min over the support
+ *                              entries with finite limits, lower < upper and a finite upper - lower (a free-flyer's entries, whose
+ *                              limits are -+DBL_MAX, take no part); 0 when the support has none.  q_ref and w are not read.
+ *   IKGPU_PICK_MANIPULABILITY  1 / sqrt(det(J J^T + damping^2 I)), J the M-row weighted task Jacobian ikgpu_evaluate_batch defines at
+ *                              q_k: the product of the pivots of the L D L^T factor the solver forms.  q_ref and w are not read.
+ * Plain entries are compared, as in the solution set: no distance modulo 2 pi, prismatic entries in metres.  q_ref: DEVICE [nq x B] in
+ * the batch layout, or NULL: q0.  w: HOST [nq], finite and >= 0, or NULL: ones; it is read during the call.
+ * IKGPU_ERR_INVALID: an unknown rule, K outside 1 .. 64, w with a negative or non-finite entry, a workspace that is too small, and the
+ * never-stop visitor (stop_sq_tol < 0 and no derived visitor: no start converges and the rule could never act, as in the solution
+ * set).  q_out must not overlap q0, starts or q_ref.  DEVICE pointers otherwise; asynchronous on `stream`; B == 0 is a no-op.
+ * A chain problem under the reference's visitor with K in {2, 4, 8, 16, 32, 64} runs ONE launch (`dls_chain_pick<...>`) with the
+ * multi-start kernel's lane mapping: one trailing evaluation after the loop, the cost, the key, the selection across lanes, the
+ * winner's stores (no LDS, no queue slot, no allocation: capturable in a graph; `workspace` is not read; w travels in the kernel
+ * arguments).  Every other case -- tree, generic, static-program and derived-visitor problems, K = 1, K not a power of two -- runs the
+ * definition from inside the call, start after start, in `workspace` (DEVICE memory of at least ikgpu_dls_pick_workspace_bytes bytes);
+ * when a step fails, ikgpu_last_error() names the start. */
+typedef enum { IKGPU_PICK_DISTANCE = 0, IKGPU_PICK_MAX_DISTANCE = 1, IKGPU_PICK_LIMIT_MARGIN = 2, IKGPU_PICK_MANIPULABILITY = 3 } ikgpu_pick_rule;
+int ikgpu_dls_pick_batch(const ikgpu_problem *p, int64_t B, int32_t K, const double *q0, const double *starts, uint64_t seed,
+                         const double *targets, const ikgpu_dls_params *params, int32_t rule /* ikgpu_pick_rule */,
+                         const double *q_ref /* DEVICE [nq x B], or NULL: q0 */, const double *w /* HOST [nq], or NULL: ones */,
+                         double *q_out, uint8_t *success, int32_t *iters, int32_t *winner, double *cost, double *err_sq,
+                         int layout /* ikgpu_layout */, void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of `workspace` ikgpu_dls_pick_batch needs for these arguments, whatever the rule: 0 for the single launch. */
+size_t ikgpu_dls_pick_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, const ikgpu_dls_params *params);
+/* Name of what ikgpu_dls_pick_batch runs with these parameters, K and rule: `dls_chain_pick<NJ=6,full,hot>` (or hot-rtc / general: the
+ * build ikgpu_problem_kernel reports) for the single launch, `loop(<ikgpu_problem_kernel's name>)` for the definition run start after
+ * start; "" for an unknown rule.  The string belongs to the calling thread and lasts until its next call. */
+const char *ikgpu_dls_pick_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K, int32_t rule);
+
 /* ---- solution set: the DISTINCT converged starts among K starts per problem, up to N of them.  An IK target rarely has one solution
  * (a 6-joint arm has up to eight branches, a 7-joint chain a whole family) and ik::dls, a local method, finds the one its start leads
  * to (reference ik/ik/dls.cpp:10 "todo - if limited convergence, try random walk"; dls.cpp:73 "If issues, perform random restart";
