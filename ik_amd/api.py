@@ -477,6 +477,18 @@ def plan(problem):
     return buf.value.decode()
 
 
+def tree_build(problem, visitor=None, p=None, pik_levels=0):
+    """Which compile-time build of the tree kernel a solve of the problem launches (host-only, include/ikgpu.h
+    ikgpu_dls_tree_build_plan): "<build>,<folded|unfolded>,<extras>,refill=<twin>", or "" when the solve does not run on the tree
+    kernel.  pik_levels: 0 for dls / dls_batch, 1 or 2 for pik with that many levels."""
+    arr = _task_table(problem)
+    cons, ncons = _constraint_table(problem)
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    buf = C.create_string_buffer(160)
+    capi.check(capi.lib().ikgpu_dls_tree_build_plan(problem.model()._h, arr, len(arr), cons, ncons, C.byref(prm), pik_levels, buf, len(buf)))
+    return buf.value.decode()
+
+
 def precompile(problem):
     """Compile ahead of time (host-only, no device) what dls_data(problem) would compile at run time -- the structure-specialised
     chain kernel of a chain without a pre-built instantiation -- into the on-disk cache; returns the kernel name.  Raises

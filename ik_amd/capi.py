@@ -28,7 +28,7 @@ SYMBOLS = [
     "ikgpu_problem_plan",
     "ikgpu_dls_solve_batch", "ikgpu_dls_solve_batch_host", "ikgpu_evaluate_batch", "ikgpu_task_frames_fk_batch",
     "ikgpu_pik_params_default", "ikgpu_pik_solve_batch", "ikgpu_pik_solve_batch_host", "ikgpu_pik_kernel",
-    "ikgpu_problem_create_constrained", "ikgpu_problem_plan_constrained", "ikgpu_problem_support",
+    "ikgpu_problem_create_constrained", "ikgpu_problem_plan_constrained", "ikgpu_problem_support", "ikgpu_dls_tree_build_plan",
     "ikgpu_problem_precompile", "ikgpu_rtc_worker_compile",
     "ikgpu_shard_range", "ikgpu_shard_slot_layout", "ikgpu_shard_slot_bytes", "ikgpu_shard_group_create", "ikgpu_shard_group_destroy",
     "ikgpu_shard_group_size", "ikgpu_shard_group_problem", "ikgpu_shard_group_uses_rccl", "ikgpu_shard_group_stream",
@@ -126,6 +126,8 @@ def lib():
     L.ikgpu_problem_create_constrained.argtypes = [vp, C.POINTER(Task), i32, C.POINTER(Task), i32, i32, C.POINTER(vp)]
     L.ikgpu_problem_plan_constrained.argtypes = [vp, C.POINTER(Task), i32, C.POINTER(Task), i32, C.c_char_p, sz]
     L.ikgpu_problem_precompile.argtypes = [vp, C.POINTER(Task), i32, C.POINTER(Task), i32, C.c_char_p, sz]
+    L.ikgpu_dls_tree_build_plan.argtypes = [vp, C.POINTER(Task), i32, C.POINTER(Task), i32, C.POINTER(DlsParams), i32, C.c_char_p, sz]
+    L.ikgpu_dls_tree_build_plan.restype = C.c_int
     L.ikgpu_shard_range.argtypes = [i64, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     L.ikgpu_shard_range.restype = None
     L.ikgpu_shard_slot_layout.argtypes = [i32, i64, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]

@@ -710,6 +710,31 @@ int ikgpu_problem_plan_constrained(const ikgpu_model *h, const ikgpu_task *tasks
     });
 }
 
+int ikgpu_dls_tree_build_plan(const ikgpu_model *h, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
+                              int32_t nconstraints, const ikgpu_dls_params *params, int32_t pik_levels, char *out, size_t cap) {
+    if (int rc = check_problem_inputs(h, tasks, constraints, nconstraints)) return rc;
+    if (int rc = check_have_params(params)) return rc;
+    if (int rc = refuse_if(pik_levels < 0 || pik_levels > 2, "pik_levels must be 0 (ik::dls), 1 or 2")) return rc;
+    return guarded([&] {
+        const KernelPlan k = plan_kernels(h->m, tasks, ntasks, constraints, nconstraints, /*compile=*/false);
+        std::string name;
+        if (k.host.kind == ikgpu::KernelKind::Tree) {
+            // ik::pik with two levels goes to the tree kernel by itself (ikgpu_pik_solve_batch); with one level it is the DLS iteration
+            // and takes ik::dls's route (dispatch_dls: the static lane program first where the plan prefers it, a derived visitor never here)
+            const bool pik_tree = pik_levels == 2 && k.gen.generic.nlevels == 2 && k.host.constraints.empty() && !pik_forced(/*or_static=*/true) &&
+                                  ikgpu::tree_takes_two_level_pik(k.host);
+            const bool dls_tree = pik_levels != 2 && !(pik_levels == 1 && (k.gen.generic.nlevels != 1 || !k.host.constraints.empty() || pik_forced(true))) &&
+                                  !k.dls_on_static_gen && !ikgpu::visitor_extended(*params);
+            if (pik_tree || dls_tree) {
+                const ikgpu::TreeBuild b = ikgpu::select_tree_build(k.host, *params, pik_tree);
+                if (b.launchable) name = ikgpu::tree_build_name(b);
+            }
+        }
+        copy_name(name, out, cap);
+        return static_cast<int>(IKGPU_OK);
+    });
+}
+
 int ikgpu_problem_precompile(const ikgpu_model *h, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
                              int32_t nconstraints, char *out, size_t cap) {
     if (int rc = check_problem_inputs(h, tasks, constraints, nconstraints)) return rc;

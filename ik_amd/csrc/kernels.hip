@@ -20,6 +20,7 @@
 #include "device/pik_solver.hpp"
 #include "device/tree_kernel_body.hpp"
 #include "generic_tables.hpp"
+#include "tree_build.hpp"
 
 namespace ikgpu {
 namespace {
@@ -904,26 +905,13 @@ TreeKernelArgs<NJ, NCH> make_tree_args(const ProblemHost &ph, const DeviceTables
 }
 
 }  // namespace
-// kernels_tree_refill.hip: the resident waves of a lock-step build's refill twin (0: it has none), and its launch
+// kernels_tree_refill.hip: the resident waves of a lock-step build's refill twin (TreeBuild::refill; 0: it has none), and its launch
 template <int NJ, int NCH>
-int64_t tree_refill_waves(const ProblemHost &ph, int build, int64_t B);
+int64_t tree_refill_waves(int refill, int64_t B);
 template <int NJ, int NCH>
-hipError_t launch_tree_refill_build(const ikdev::TreeKernelArgs<NJ, NCH> &a, int build, int64_t waves, unsigned long long *queue, int chunk,
+hipError_t launch_tree_refill_build(const ikdev::TreeKernelArgs<NJ, NCH> &a, int refill, int64_t waves, unsigned long long *queue, int chunk,
                                     hipStream_t stream);
 namespace {
-
-template <int NJ>
-bool tree_hot_structure_matches(const ProblemHost &ph) {
-    if constexpr (std::is_same<typename ikdev::TreeHotStruct<NJ>::type, void>::value) return true;   // no structure folded for this NJ
-    else {
-        for (const ChainHost *c : {&ph.chain, &ph.chainB}) {
-            if (c->nj == 0) continue;
-            const ChainStructure s = chain_structure(*c);
-            if (!s.fits || s.code[0] != ikdev::kTreeHotCode7[0] || s.code[1] != ikdev::kTreeHotCode7[1] || s.code[2] != ikdev::kTreeHotCode7[2]) return false;
-        }
-        return true;
-    }
-}
 
 template <int NJ, int NCH>
 hipError_t run_dls_tree(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm,
@@ -931,59 +919,34 @@ hipError_t run_dls_tree(const ProblemHost &ph, const DeviceTables &dt, const Bat
     TreeKernelArgs<NJ, NCH> a = make_tree_args<NJ, NCH>(ph, dt);
     fill_solve_args(a, io, prm);
     if (pik_lambda1) { a.prm.pik_on = 1; a.prm.pik_lam2_1 = *pik_lambda1 * *pik_lambda1; }
-    // hot build: both chains carry the shape's known placement mask, every task is Full with unit weights and the base
-    // task sits at a pure translation from the base joint -- all folded at compile time; otherwise the general build
-    constexpr int kMask = HotMask<NJ>::value;
-    constexpr int kHot = kMask | (1 << ikdev::kSpecUnit) | (1 << ikdev::kSpecUnitP) | (1 << ikdev::kSpecIdP);
-    // (and, where the hot builds fold the chains' placement STRUCTURE -- ikdev::TreeHotStruct, NJ = 7 -- both chains carry that code)
-    const bool hot = !ph.tree_extras() && kMask != 0 && (a.prm.idmask[0] & kMask) == kMask && (NCH == 1 || (a.prm.idmask[1] & kMask) == kMask) &&
-                     a.prm.unit[0] && (NCH == 1 || a.prm.unit[1]) && (!a.prm.hasP || (a.prm.unitP && (a.prm.idmaskP & 1))) &&
-                     tree_hot_structure_matches<NJ>(ph);
+    // which compile-time build: problem.cpp select_tree_build decides (hot / hot-never / mask / general, the placement mask folded or
+    // not, the extras); tree_build.hpp maps its answer onto SPEC
+    const TreeBuild build = select_tree_build(ph, prm, pik_lambda1 != nullptr);
+    if (!build.launchable) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>((io.B + kTreeBlock - 1) / kTreeBlock));
-    // in between (as for the chain kernels): the placement mask folded, weights / task types / base-frame placement general
-    // (A/B on one box, full body: pelvis task weighted 1.07 -> 0.91 ms, feet as Position tasks 0.98 -> 0.83 ms)
-    const bool structure = tree_hot_structure_matches<NJ>(ph);
-    const bool mask_only = !hot && !ph.tree_extras() && structure && kMask != 0 && (a.prm.idmask[0] & kMask) == kMask && (NCH == 1 || (a.prm.idmask[1] & kMask) == kMask);
-    // the general builds (extras: base reference, alignment row, fixed base, posture rows, the constraint, level 1 of ik::pik) exist
-    // twice where the shape's mask is known: with it folded (bit kSpecGen next to the mask) and without
-    const bool fold = structure && kMask != 0 && (a.prm.idmask[0] & kMask) == kMask && (NCH == 1 || (a.prm.idmask[1] & kMask) == kMask);
-    const size_t post_lds = NCH == 1 ? sizeof(double) * kTreeBlock * static_cast<size_t>(2 * std::max(1, a.prm.post_n) + NJ) : 0;
-#define IKGPU_TREE_GENERAL(FLAGS, LDS)                                                                                              \
-    do {                                                                                                                            \
-        if (fold) hipLaunchKernelGGL((dls_tree_kernel<NJ, NCH, (kMask != 0 ? ((FLAGS) | kMask | (1 << ikdev::kSpecGen)) : (FLAGS))>), grid, \
-                                     dim3(kTreeBlock), LDS, stream, a);                                                             \
-        else hipLaunchKernelGGL((dls_tree_kernel<NJ, NCH, (FLAGS)>), grid, dim3(kTreeBlock), LDS, stream, a);                       \
-    } while (0)
+    // the posture build with one chain keeps the outside joints and the posture targets in dynamic LDS (dls_tree_kernel)
+    const size_t post_lds = NCH == 1 && build.build == TreeBuild::kGeneral && build.extras == TreeBuild::kPosture
+                                ? sizeof(double) * kTreeBlock * static_cast<size_t>(2 * std::max(1, a.prm.post_n) + NJ) : 0;
+    // (next to the kernel's static LDS -- the park buffer's one row per wave and the table -- that passes the default 64 KB per
+    // workgroup from 28 rows outside the chain on: the kernel's limit is raised first, as for the cooperative kernels, to what
+    // kMaxPostOut rows take)
+    const size_t static_lds = sizeof(double) * kTreeWaves * 64 + sizeof(TreeDesc<NJ, NCH>);
+    const size_t post_lds_max = sizeof(double) * kTreeBlock * static_cast<size_t>(2 * ikdev::kMaxPostOut + NJ);
     auto launch_lockstep = [&]() {
-    if (hot && !(a.prm.stop_sq_tol >= 0.0) && !std::getenv("IKGPU_TREE_NEVER_OFF"))   // the never-stop visitor: its own instantiation, as the hot chain kernel's
-        hipLaunchKernelGGL((dls_tree_kernel<NJ, NCH, (kHot | (1 << ikdev::kSpecNever))>), grid, dim3(kTreeBlock), 0, stream, a);
-    else if (hot) hipLaunchKernelGGL((dls_tree_kernel<NJ, NCH, kHot>), grid, dim3(kTreeBlock), 0, stream, a);
-    else if (mask_only) hipLaunchKernelGGL((dls_tree_kernel<NJ, NCH, (kMask != 0 ? kMask : kHot)>), grid, dim3(kTreeBlock), 0, stream, a);
-    else if (pik_lambda1)   // two-level ik::pik (tree_takes_two_level_pik): the general build + the level-1 row's projection
-        IKGPU_TREE_GENERAL((1 << ikdev::kSpecPik), 0);
-    else if (ph.cons_on) {   // one FrameConstraint on the second chain: the constraint build (general + the projection), with or
-                             // without the posture code
-        if constexpr (NCH == 2) {
-            if (ph.has_posture) IKGPU_TREE_GENERAL(ikdev::kSpecPostCons, 0);
-            else IKGPU_TREE_GENERAL((1 << ikdev::kSpecCons), 0);
-        }
-    } else if (ph.has_posture)
-        IKGPU_TREE_GENERAL((1 << ikdev::kSpecPost), post_lds);
-    else IKGPU_TREE_GENERAL(0, 0);
-    return hipGetLastError();
+        bool raised = true;
+        const bool built = with_tree_spec<NJ, NCH>(build, [&](auto spec) {
+            if (post_lds) raised = raise_lds_limit(reinterpret_cast<const void *>(&dls_tree_kernel<NJ, NCH, decltype(spec)::value>), post_lds + static_lds, post_lds_max);
+            if (raised) hipLaunchKernelGGL((dls_tree_kernel<NJ, NCH, decltype(spec)::value>), grid, dim3(kTreeBlock), post_lds, stream, a);
+        });
+        const hipError_t e = hipGetLastError();   // (also what a refused limit left behind: the next launch must not find it)
+        return !built ? hipErrorInvalidValue : !raised && e == hipSuccess ? hipErrorInvalidValue : e;
     };
-    if constexpr (NCH != 2) {
-        if (ph.cons_on && !pik_lambda1 && !hot && !mask_only) return hipErrorInvalidValue;
-    }
     // stop-rule mode on a batch larger than the machine: lane refill (kernels_tree_refill.hip) for the builds that have it -- every
     // build without per-lane state outside q (no posture rows, no constraint, no ik::pik level) -- directly, or as the second phase
     // after the lock-step kernel's first iterations (kernels.hpp run_stop_rule; the never-stop visitor runs lock-step)
-    const int build = hot ? kTreeBuildHot : mask_only ? kTreeBuildMask : fold ? kTreeBuildFold : kTreeBuildGeneral;
-    const int64_t waves = !pik_lambda1 && prm.stop_sq_tol >= 0.0 && prm.max_iterations >= 1 ? tree_refill_waves<NJ, NCH>(ph, build, io.B) : 0;
-    const hipError_t e = run_stop_rule(dt.queues, io, prm, stream, a, true, waves, PassThrough{&ph, &dt}, launch_lockstep,
-                                       [&](unsigned long long *queue, int chunk) { return launch_tree_refill_build<NJ, NCH>(a, build, waves, queue, chunk, stream); });
-#undef IKGPU_TREE_GENERAL
-    return e;
+    const int64_t waves = prm.stop_sq_tol >= 0.0 && prm.max_iterations >= 1 ? tree_refill_waves<NJ, NCH>(build.refill, io.B) : 0;
+    return run_stop_rule(dt.queues, io, prm, stream, a, true, waves, PassThrough{&ph, &dt}, launch_lockstep,
+                         [&](unsigned long long *queue, int chunk) { return launch_tree_refill_build<NJ, NCH>(a, build.refill, waves, queue, chunk, stream); });
 }
 
 template <int NJ, int NCH>
@@ -1190,7 +1153,9 @@ __global__ __launch_bounds__(kBlock) void pik_coop_kernel(const ikdev::PikCoopKe
 }  // namespace
 
 // A launch asking for more than the default 64 KB of dynamic LDS has to raise the kernel's limit first (once per kernel and device).
-bool raise_lds_limit(const void *kernel, size_t lds) {
+// limit: the dynamic size asked for -- the CU's 160 KB for a kernel without static LDS; a kernel that has some states its own (the
+// runtime refuses a dynamic limit that does not fit next to the static part).
+bool raise_lds_limit(const void *kernel, size_t lds, size_t limit) {
     if (lds <= 64 * 1024) return true;
     static std::mutex mu;
     static std::vector<std::pair<const void *, int>> done;   // (kernel, device) pairs already raised
@@ -1199,7 +1164,7 @@ bool raise_lds_limit(const void *kernel, size_t lds) {
     std::lock_guard<std::mutex> lock(mu);
     for (const auto &d : done)
         if (d.first == kernel && d.second == dev) return true;
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(limit)) != hipSuccess) return false;
     done.emplace_back(kernel, dev);
     return true;
 }

@@ -245,8 +245,7 @@ int stop_rule_mode(const ikgpu_dls_params &prm, int64_t B, int64_t resident_wave
 // the static lane programs take the tree kernels' (profiles/r04_refill_timing_static.txt).
 int two_phase_iterations(bool tree);
 int two_phase_active(bool tree);
-// the lock-step builds of the tree kernel a refill launch can mirror (kernels.hip run_dls_tree / kernels_tree_refill.hip)
-enum { kTreeBuildGeneral = 0, kTreeBuildHot = 1, kTreeBuildMask = 2, kTreeBuildFold = 3 };
+// (the lock-step builds of the tree kernel a refill launch can mirror: problem.hpp TreeBuild::refill)
 int64_t refill_grid(const void *kernel, int64_t B);
 int64_t refill_resident(int64_t occupancy_waves, int64_t B);   // persistent waves of a refill launch given what the device can hold
 int refill_chunk(int64_t B, int64_t grid);   // problems a wave reserves per pull from the head (IKGPU_REFILL_CHUNK overrides) | refill_batch() << 16
@@ -353,7 +352,7 @@ hipError_t rtc_launch_chain_hot(const ProblemHost &ph, const DeviceTables &dt, c
                                 hipStream_t stream);
 hipError_t launch_targets_from_pose7(int64_t B, int ntasks, const double *pose7, double *targets12, int layout, hipStream_t stream);
 int64_t persistent_grid(const void *kernel, int block, size_t lds, int64_t nblocks);
-bool raise_lds_limit(const void *kernel, size_t lds);
+bool raise_lds_limit(const void *kernel, size_t lds, size_t limit = 160 * 1024);
 hipError_t launch_dls_chain_hot(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
                                 hipStream_t stream);
 

@@ -38,47 +38,49 @@ __global__ __launch_bounds__(kTreeBlock) void dls_tree_refill_kernel(const TreeK
 }
 
 // The refill twin of each lock-step build (kernels.hip run_dls_tree), whose lane program it must share to return the same bits:
-// kTreeBuildHot (mask, unit weights, base task at a translation: all folded), kTreeBuildMask (the placement mask folded only),
-// kTreeBuildFold (the mask next to the general extras: base-relative references, alignment row, fixed base), kTreeBuildGeneral.
-// Instantiated for NJ = 7 only.
+// TreeBuild::kRefillHot (mask, unit weights, base task at a translation: all folded), kRefillMask (the placement mask folded only),
+// kRefillFold (the mask next to the general extras: base-relative references, alignment row, fixed base), kRefillGeneral.
+// Instantiated for NJ = 7 only (problem.cpp select_tree_build names a twin for no other shape).
 template <int NJ, int NCH>
-const void *refill_kernel(int build) {
+const void *refill_kernel(int refill) {
     if constexpr (NJ != 7) {
         return nullptr;
     } else {
         constexpr int kMask = HotMask<NJ>::value;
         constexpr int kHot = kMask | (1 << ikdev::kSpecUnit) | (1 << ikdev::kSpecUnitP) | (1 << ikdev::kSpecIdP);
         constexpr int kFold = kMask | (1 << ikdev::kSpecGen);
-        return build == kTreeBuildHot    ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, kHot>)
-               : build == kTreeBuildMask ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, kMask>)
-               : build == kTreeBuildFold ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, kFold>)
-                                         : reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, 0>);
+        return refill == TreeBuild::kRefillHot    ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, kHot>)
+               : refill == TreeBuild::kRefillMask ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, kMask>)
+               : refill == TreeBuild::kRefillFold ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, kFold>)
+               : refill == TreeBuild::kRefillGeneral ? reinterpret_cast<const void *>(dls_tree_refill_kernel<NJ, NCH, 0>)
+                                                     : nullptr;
     }
 }
 
 }  // namespace
 
-// Resident waves of the refill twin of a tree problem's lock-step build (kernels.hpp run_stop_rule); 0 where it has none: posture rows,
-// a constraint, shapes other than Cassie's (ik::pik levels: the caller passes none).  Persistent workgroups of two waves: what the device
+// Resident waves of the refill twin of a tree problem's lock-step build (kernels.hpp run_stop_rule); 0 where it has none
+// (TreeBuild::kRefillNone: posture rows, a constraint, an ik::pik level, shapes other than NJ = 7).  Persistent workgroups of two waves: what the device
 // holds, one wave per SIMD until every lane has >= 8 problems (kernels.hip refill_resident).
 template <int NJ, int NCH>
-int64_t tree_refill_waves(const ProblemHost &ph, int build, int64_t B) {
-    if (NJ != 7 || ph.has_posture || ph.cons_on) return 0;
-    const int64_t occ_waves = persistent_grid(refill_kernel<NJ, NCH>(build), kTreeBlock, 0, INT64_MAX) * kTreeWaves;
+int64_t tree_refill_waves(int refill, int64_t B) {
+    const void *kernel = refill_kernel<NJ, NCH>(refill);
+    if (!kernel) return 0;
+    const int64_t occ_waves = persistent_grid(kernel, kTreeBlock, 0, INT64_MAX) * kTreeWaves;
     const int64_t waves = refill_resident(occ_waves, B);
     return std::max<int64_t>(kTreeWaves, waves / kTreeWaves * kTreeWaves);
 }
 
-// The refill twin of `build` on `waves` resident waves (tree_refill_waves), `a` the lock-step launch's argument block.
+// The refill twin `refill` on `waves` resident waves (tree_refill_waves), `a` the lock-step launch's argument block.
 template <int NJ, int NCH>
-hipError_t launch_tree_refill_build(const TreeKernelArgs<NJ, NCH> &a, int build, int64_t waves, unsigned long long *queue, int chunk,
+hipError_t launch_tree_refill_build(const TreeKernelArgs<NJ, NCH> &a, int refill, int64_t waves, unsigned long long *queue, int chunk,
                                     hipStream_t stream) {
     void *args[] = {const_cast<TreeKernelArgs<NJ, NCH> *>(&a), &queue, &chunk};
-    return hipLaunchKernel(refill_kernel<NJ, NCH>(build), dim3(static_cast<unsigned>(waves / kTreeWaves)), dim3(kTreeBlock), args, 0, stream);
+    return hipLaunchKernel(refill_kernel<NJ, NCH>(refill), dim3(static_cast<unsigned>(waves / kTreeWaves)), dim3(kTreeBlock), args, 0, stream);
 }
 
 #define X(N, C)                                                                                                                        \
-    template int64_t tree_refill_waves<N, C>(const ProblemHost &, int, int64_t);                                                       \
+    template int64_t tree_refill_waves<N, C>(int, int64_t);                                                                            \
     template hipError_t launch_tree_refill_build<N, C>(const TreeKernelArgs<N, C> &, int, int64_t, unsigned long long *, int, hipStream_t);
 X(7, 2) X(7, 1) X(6, 2) X(6, 1)
 #undef X

@@ -3,8 +3,12 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+#include <type_traits>
+
+#include "device/tree_kernel_body.hpp"   // ikdev::HotMask, ikdev::kTreeHotCode7: the constants the tree builds are compiled for
 
 namespace ikgpu {
 namespace {
@@ -737,6 +741,69 @@ TreeArgsHost tree_args(const ProblemHost &ph) {
             a.postc_m[c][j] = ph.posture_chain_mask[c][j];
         }
     return a;
+}
+
+namespace {
+
+// the placement mask a tree shape's folded builds are compiled for (0: the shape has none)
+int tree_hot_mask(int nj) { return nj == 7 ? ikdev::HotMask<7>::value : nj == 6 ? ikdev::HotMask<6>::value : 0; }
+
+// ... and, where they also fold the chains' placement STRUCTURE (ikdev::TreeHotStruct, NJ = 7), whether both chains carry that code
+bool tree_hot_structure_matches(const ProblemHost &ph) {
+    if (ph.chain.nj != 7) return true;   // no structure folded for this NJ
+    for (const ChainHost *c : {&ph.chain, &ph.chainB}) {
+        if (c->nj == 0) continue;
+        const ChainStructure s = chain_structure(*c);
+        if (!s.fits || s.code[0] != ikdev::kTreeHotCode7[0] || s.code[1] != ikdev::kTreeHotCode7[1] || s.code[2] != ikdev::kTreeHotCode7[2]) return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+TreeBuild select_tree_build(const ProblemHost &ph, const ikgpu_dls_params &prm, bool pik) {
+    static_assert(std::is_same<ikdev::TreeHotStruct<6>::type, void>::value && !std::is_same<ikdev::TreeHotStruct<7>::type, void>::value,
+                  "tree_hot_structure_matches: the shapes with a folded structure code");
+    const TreeArgsHost a = tree_args(ph);
+    const int mask = tree_hot_mask(ph.chain.nj), nch = a.nch;
+    const bool carries = mask != 0 && (a.idmask[0] & mask) == mask && (nch == 1 || (a.idmask[1] & mask) == mask);
+    const bool structure = tree_hot_structure_matches(ph);
+    TreeBuild b;
+    // hot: both chains carry the shape's known placement mask, every task is Full with unit weights and the base task sits at a
+    // pure translation from the base joint -- all folded at compile time
+    const bool hot = !ph.tree_extras() && carries && a.unit[0] && (nch == 1 || a.unit[1]) && (!a.hasP || (a.unit[2] && (a.idmaskP & 1))) && structure;
+    // in between (as for the chain kernels): the placement mask folded, weights / task types / base-frame placement general
+    const bool mask_only = !hot && !ph.tree_extras() && structure && carries;
+    if (hot) {   // the never-stop visitor: its own instantiation, as the hot chain kernel's
+        b.build = !(prm.stop_sq_tol >= 0.0) && !std::getenv("IKGPU_TREE_NEVER_OFF") ? TreeBuild::kHotNever : TreeBuild::kHot;
+        b.folded = true;
+        b.refill = TreeBuild::kRefillHot;
+    } else if (mask_only) {
+        b.build = TreeBuild::kMask;
+        b.folded = true;
+        b.refill = TreeBuild::kRefillMask;
+    } else {
+        // the general builds exist twice where the shape's mask is known: with it folded and without
+        b.build = TreeBuild::kGeneral;
+        b.folded = structure && carries;
+        b.extras = pik                          ? TreeBuild::kPik
+                   : ph.cons_on && ph.has_posture ? TreeBuild::kPostureConstraint
+                   : ph.cons_on                   ? TreeBuild::kConstraint
+                   : ph.has_posture               ? TreeBuild::kPosture
+                                                  : TreeBuild::kNone;
+        b.refill = b.folded ? TreeBuild::kRefillFold : TreeBuild::kRefillGeneral;
+        b.launchable = nch == 2 || !ph.cons_on || pik;
+    }
+    // refill twins: NJ = 7 only, and only builds without per-lane state outside q (no posture rows, no constraint, no ik::pik level)
+    if (ph.chain.nj != 7 || ph.has_posture || ph.cons_on || pik) b.refill = TreeBuild::kRefillNone;
+    return b;
+}
+
+std::string tree_build_name(const TreeBuild &b) {
+    static const char *const kBuild[] = {"hot", "hot-never", "mask", "general"};
+    static const char *const kExtras[] = {"none", "posture", "constraint", "posture+constraint", "pik"};
+    static const char *const kRefill[] = {"none", "hot", "mask", "fold", "general"};
+    return std::string(kBuild[b.build]) + (b.folded ? ",folded," : ",unfolded,") + kExtras[b.extras] + ",refill=" + kRefill[b.refill];
 }
 
 std::vector<uint8_t> multistart_draw_mask(const Model &m, const ProblemHost &ph) {

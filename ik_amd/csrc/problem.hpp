@@ -169,6 +169,31 @@ struct TreeArgsHost {
 };
 TreeArgsHost tree_args(const ProblemHost &ph);
 
+// Which of the tree kernel's compile-time builds a Tree problem launches.  The kernel name says none of it (the build depends on
+// the chains' placements, the weights and the stop rule), so this is the ONE place that decides: kernels.hip run_dls_tree and
+// kernels_tree_refill.hip dispatch on the result (tree_build.hpp maps it onto the SPEC template argument), the CPU lane emulator
+// under tests/ does, and ikgpu_dls_tree_build_plan reports it.
+//   hot        both chains carry the shape's placement mask (and structure code), every task Full with unit weights, the base
+//              task at a pure translation from the base joint: all folded.  hot-never: the same under the never-stop visitor
+//              (stop_sq_tol < 0; IKGPU_TREE_NEVER_OFF keeps it off)
+//   mask       the placement mask folded, weights / task types / base-frame placement general
+//   general    a base-relative reference, an alignment row, a fixed base, posture rows, the constraint or level 1 of a two-level
+//              ik::pik -- with the placement mask folded where the chains carry it, else without
+struct TreeBuild {
+    enum { kHot = 0, kHotNever, kMask, kGeneral };
+    enum { kNone = 0, kPosture, kConstraint, kPostureConstraint, kPik };
+    enum { kRefillNone = 0, kRefillHot, kRefillMask, kRefillFold, kRefillGeneral };
+    int build = kGeneral;
+    bool folded = false;        // the placement mask is a compile-time constant of the build (always in hot / mask)
+    int extras = kNone;         // what the general build adds (kNone in hot / mask)
+    int refill = kRefillNone;   // the refill twin a stop-rule solve of the problem would use (kernels_tree_refill.hip)
+    bool launchable = true;     // false: a constraint on a one-chain shape, which has no build
+};
+// pik: level 1 of a two-level ik::pik rides on the launch (kernels.hpp tree_takes_two_level_pik holds).  Reads prm.stop_sq_tol only.
+TreeBuild select_tree_build(const ProblemHost &ph, const ikgpu_dls_params &prm, bool pik);
+// "hot,folded,none,refill=hot", "general,unfolded,posture+constraint,refill=none", ...
+std::string tree_build_name(const TreeBuild &b);
+
 // Which entries of q a GENERATED start of a multi-start solve draws (include/ikgpu.h ikgpu_multistart_starts): in the task support, of a
 // revolute or prismatic joint, with finite limits lower < upper.  Every other entry -- the free-flyer's seven, an unbounded joint's --
 // keeps q0's value.  [nq], 1 = drawn.

@@ -169,6 +169,15 @@ int ikgpu_problem_create_constrained(const ikgpu_model *m, const ikgpu_task *tas
                                      int32_t nconstraints, int32_t device, ikgpu_problem **out);
 int ikgpu_problem_plan_constrained(const ikgpu_model *m, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
                                    int32_t nconstraints, char *out, size_t cap);
+/* Host-only, touches no device: WHICH compile-time build of the free-flyer tree kernel a solve of this problem with these parameters
+ * launches -- the kernel name (`dls_tree<...>`) does not say, it depends on the chains' placements, the weights and the stop rule.
+ * Writes "<build>,<folded|unfolded>,<extras>,refill=<twin>" with build hot | hot-never | mask | general, extras none | posture |
+ * constraint | posture+constraint | pik and twin (the refill kernel a stop-rule solve larger than the machine would use) hot | mask |
+ * fold | general | none -- or "" when the solve does not run on the tree kernel.  pik_levels: 0 for ikgpu_dls_solve_batch (params:
+ * its parameters, of which stop_sq_tol is read), 1 or 2 for ikgpu_pik_solve_batch with that many levels, no secondary step and
+ * lambda > 0 (params as the level-0 DLS parameters).  The launcher dispatches on the same selection that this reports. */
+int ikgpu_dls_tree_build_plan(const ikgpu_model *m, const ikgpu_task *tasks, int32_t ntasks, const ikgpu_task *constraints,
+                              int32_t nconstraints, const ikgpu_dls_params *params, int32_t pik_levels, char *out, size_t cap);
 /* Host-only, touches no device: compiles ahead of time whatever ikgpu_problem_create would compile at run time for this problem
  * -- today the structure-specialised chain kernel (`dls_chain<..,hot-rtc>`) of a fixed-base chain whose placement structure has no
  * pre-built instantiation, through hipRTC -- and leaves the code object in the on-disk cache ($IKGPU_CACHE_DIR, else
