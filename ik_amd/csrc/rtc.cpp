@@ -465,6 +465,14 @@ bool run_worker(const std::string &dir, const char *prefix, const std::string &s
     return ok;
 }
 
+// IKGPU_RTC_DUMP=<dir>: the generated source (defines included) is written there under the name of its code object.
+void dump_source(const char *name, const std::string &src) {
+    if (const char *dump = std::getenv("IKGPU_RTC_DUMP")) {
+        std::vector<char> text(src.begin(), src.end());
+        (void)write_file_atomically(std::string(dump) + name + ".hip", text);
+    }
+}
+
 // Fetches the code object of `src_in` from the on-disk cache or has it compiled (file name: prefix + object_key).
 // IKGPU_RTC_DUMP=<dir>: also writes the generated source there.  Called WITHOUT g_mu.
 void compile_cached(const char *prefix, const std::string &src_in, HotCode &hc, bool if_convert = false) {
@@ -476,10 +484,7 @@ void compile_cached(const char *prefix, const std::string &src_in, HotCode &hc, 
     const uint64_t key = object_key(src, flags);
     char name[96];
     std::snprintf(name, sizeof name, "/%s_%016llx", prefix, static_cast<unsigned long long>(key));
-    if (const char *dump = std::getenv("IKGPU_RTC_DUMP")) {
-        std::vector<char> text(src.begin(), src.end());
-        (void)write_file_atomically(std::string(dump) + name + ".hip", text);
-    }
+    dump_source(name, src);
     const std::string dir = cache_dir();
     const std::string path = dir.empty() ? std::string() : dir + name + ".hsaco";
     if (!path.empty() && read_cached_object(path, key, hc.code)) { hc.ok = true; hc.log = "cached: " + path; return; }
@@ -506,7 +511,17 @@ HotCode &ensure_code(Map &map, const Key &key, const char *prefix, const std::st
     {
         std::lock_guard<std::mutex> lock(g_mu);
         hc = &map[key];   // (std::map: the node never moves)
-        if (hc->tried) { g_last_log = hc->log; return *hc; }
+        if (hc->tried) {
+            // (a dump is asked for per request, not per compilation: a source this process has compiled already is written too)
+            if (std::getenv("IKGPU_RTC_DUMP") && rtc_api().ok) {
+                const std::string full = with_defines(src);
+                char name[96];
+                std::snprintf(name, sizeof name, "/%s_%016llx", prefix, static_cast<unsigned long long>(object_key(full, compile_flags(if_convert))));
+                dump_source(name, full);
+            }
+            g_last_log = hc->log;
+            return *hc;
+        }
     }
     HotCode fresh;
     compile_cached(prefix, src, fresh, if_convert);

@@ -14,6 +14,7 @@ import pytest
 from conftest import ROOT
 
 import oracle as O
+import pik_rank_common as RANK
 from test_gpu_generic import CASES as GENERIC, build
 from test_gpu_constraints import CASES as CONSTRAINED
 
@@ -226,3 +227,44 @@ def test_static_pik_program_on_the_host_matches_the_oracle(tmp_path, native_buil
         q_ref, ok_ref, it_ref = O.pik_batch(om, ot, tg, q0, O.pik_params(iters, step, tol, lam, None if da is None else list(da)), 1)
         assert np.array_equal(ok, ok_ref) and np.array_equal(it, it_ref), (case, iters)
         assert np.abs(q - q_ref).max() <= 1e-6, (case, iters, np.abs(q - q_ref).max())
+
+
+def _static_pik_run(L, inp, prm_set):
+    iters, step, tol, lam, da = prm_set
+    p = lambda x: C.c_void_p(x.ctypes.data)
+    q0c, tgc, lam_a = np.ascontiguousarray(inp.q0), np.ascontiguousarray(inp.tg), np.asarray(lam, float)
+    n = q0c.shape[0]
+    q, ok, it = np.empty_like(q0c), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+    L.static_host_pik(C.c_longlong(n), p(q0c), p(tgc), iters, C.c_double(step), C.c_double(tol), len(lam), p(lam_a),
+                      p(np.ascontiguousarray(da)) if da is not None else None, p(q), p(ok), p(it))
+    return q, ok, it
+
+
+_RANK_PROGRAMS = {}
+
+
+def _rank_program(tmp_path, case):
+    """One host build per case and session."""
+    if case not in _RANK_PROGRAMS:
+        d = tmp_path / case
+        d.mkdir()
+        _RANK_PROGRAMS[case] = pik_host_program(d, RANK.inputs(case).problem)
+    return _RANK_PROGRAMS[case]
+
+
+@pytest.mark.parametrize("case", sorted(RANK.CASES))
+def test_static_pik_program_under_the_rank_rule(tmp_path, native_built, case):
+    """static_pik's pivoted Gram-Schmidt (`best > thr2 * maxpiv2`, `best > 0`) on the cases of tests/pik_rank_common.py, where keeping
+    or dropping a direction moves the answer by 1e-2 rad or more: both instantiations (the sets with da run HAS_DA = true, where
+    the last level's rows enter V too), an empty middle level (`ml == 0`, v0 = r0), an all-zero level (maxpiv2 = 0)."""
+    inp = RANK.inputs(case)
+    L = _rank_program(tmp_path, case)
+    got = {}
+    for k, prm_set in enumerate(inp.param_sets()):
+        got[k] = _static_pik_run(L, inp, prm_set)
+        inp.check("static_da" if prm_set[4] is not None else "static", prm_set, *got[k])
+    if case == "pos_w0_then_ori":   # an exact zero row leaves the answer of a row below the threshold
+        other = RANK.inputs("pos_w1e-19_then_ori")
+        Lo = _rank_program(tmp_path, other.case)
+        for k, prm_set in enumerate(other.param_sets()):
+            RANK.same_answer("static", prm_set, case, got[k][0], other.case, _static_pik_run(Lo, other, prm_set)[0])
