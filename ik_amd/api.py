@@ -18,6 +18,7 @@ like the reference's own (commented-out) tests (ik/test/dls.cpp:10-76):
 
 The C++ mirror of the same classes lives in ik_amd/csrc/host/ik/.  No arithmetic happens here.
 """
+import collections
 import ctypes as C
 import enum
 
@@ -906,6 +907,89 @@ def dls_multistart_batch(problem, Q0, targets, data, visitor=None, p=None, num_s
                                             seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
                                             win.data_ptr(), err.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
     return Q, ok, it, win, err
+
+
+PathMultistartResult = collections.namedtuple(
+    "PathMultistartResult", "q_entry entry_success entry_iterations winner err_sq reached reached_all q success iterations")
+
+
+def dls_path_multistart_kernel(data, visitor=None, p=None, num_starts=8):
+    """Name of what dls_path_multistart_batch runs for these parameters: "dls_chain_path_multistart<...>" (the scout launch, followed by
+    "dls_chain_path<...>" for the trajectory) or "loop(<data.kernel>)"."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return capi.lib().ikgpu_dls_path_multistart_kernel(data._h, C.byref(prm), num_starts).decode()
+
+
+def dls_path_multistart_batch(problem, Q0, vias, data, T, max_joint_step=0.0, visitor=None, p=None, num_starts=8, seed=0, starts=None,
+                              layout="soa", trajectory=True, out=None, stream=None):
+    """Which IK branch at the path's first pose carries the whole path?  vias[0] is that pose; the robot may move freely in joint space
+    to it.  Each of num_starts starts (dls_multistart_batch's: Q0, then `starts` or generated from `seed`) solves vias[0]; every start
+    that met the stop rule is followed along dls_path_batch(Q0 = its result, vias[1:], T, max_joint_step); the start that gets furthest
+    wins, a tie goes to the lowest index, and when no start entered the smallest error wins (include/ikgpu.h
+    ikgpu_dls_path_multistart_batch).  q_entry / entry_success / entry_iterations are dls_batch from the winning start, bit for bit;
+    reached_all[k] is start k's count, -1 where its entry failed; with trajectory=True, q / success / iterations are dls_path_batch from
+    q_entry (for the problems with entry_success = 1).  A chain problem with num_starts in {2, 4, ..., 64} runs two launches: a scout
+    that stores no trajectory, then the winner's path -- one trajectory buffer, not num_starts.
+
+    float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], vias [P, ntasks, 12, B]   |   "aos": Q0 [B, nq], vias [P, B, ntasks, 12].
+    out: a PathMultistartResult of preallocated tensors (q / success / iterations None with trajectory=False), or None.
+    Returns PathMultistartResult(q_entry, entry_success, entry_iterations, winner, err_sq, reached int32 [B], reached_all int32 [K, B],
+    q [(P-1) T, nq, B] | [(P-1) T, B, nq], success uint8 [(P-1) T, B], iterations int32 [(P-1) T, B])."""
+    import math
+    import torch
+    visitor = visitor or inverse_kinematics_visitor()
+    p = p or dls_parameters()
+    model = problem.model()
+    ntasks = problem.target_slots()
+    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    prm = _params(visitor, p)
+    _check_starts(num_starts)
+    _check_waypoints(T)
+    if not isinstance(max_joint_step, (int, float)) or not math.isfinite(max_joint_step) or max_joint_step < 0:
+        raise ValueError("max_joint_step must be finite and not negative (0: no joint-step rule), got %r" % (max_joint_step,))
+    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
+    if starts is not None and tuple(getattr(starts, "shape", ())) != (num_starts - 1,) + tuple(Q0.shape):
+        raise ValueError("starts has shape %s, expected %s" % (tuple(getattr(starts, "shape", ())), (num_starts - 1,) + tuple(Q0.shape)))
+    B, P = _check_path_inputs("dls_path_multistart_batch", Q0, vias, model, ntasks, lay, data)
+    if starts is not None:
+        _check_tensor("starts", starts, (num_starts - 1,) + tuple(Q0.shape), torch.float64, data._device)
+    N = (P - 1) * T
+    K = num_starts
+    q_shape = (N, model.nq, B) if lay == capi.SOA else (N, B, model.nq)
+    dev = Q0.device
+    if out is None:
+        r = PathMultistartResult(
+            torch.empty_like(Q0), torch.empty((B,), dtype=torch.uint8, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
+            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((K, B), dtype=torch.int32, device=dev),
+            torch.empty(q_shape, dtype=torch.float64, device=dev) if trajectory else None,
+            torch.empty((N, B), dtype=torch.uint8, device=dev) if trajectory else None,
+            torch.empty((N, B), dtype=torch.int32, device=dev) if trajectory else None)
+    else:
+        r = PathMultistartResult(*out)
+        _check_tensor("out.q_entry", r.q_entry, tuple(Q0.shape), torch.float64, data._device)
+        _check_tensor("out.entry_success", r.entry_success, (B,), torch.uint8, data._device)
+        _check_tensor("out.entry_iterations", r.entry_iterations, (B,), torch.int32, data._device)
+        _check_tensor("out.winner", r.winner, (B,), torch.int32, data._device)
+        _check_tensor("out.err_sq", r.err_sq, (B,), torch.float64, data._device)
+        _check_tensor("out.reached", r.reached, (B,), torch.int32, data._device)
+        _check_tensor("out.reached_all", r.reached_all, (K, B), torch.int32, data._device)
+        if trajectory:
+            _check_tensor("out.q", r.q, q_shape, torch.float64, data._device)
+            _check_tensor("out.success", r.success, (N, B), torch.uint8, data._device)
+            _check_tensor("out.iterations", r.iterations, (N, B), torch.int32, data._device)
+    data._bind(problem)
+    L = capi.lib()
+    nbytes = L.ikgpu_dls_path_multistart_workspace_bytes(data._h, B, K, P, T, C.byref(prm), 1 if trajectory else 0)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None   # (0 for the two launches: nothing allocated)
+    s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    capi.check(L.ikgpu_dls_path_multistart_batch(
+        data._h, B, K, P, T, Q0.data_ptr(), starts.data_ptr() if starts is not None else None, seed & 0xFFFFFFFFFFFFFFFF, vias.data_ptr(),
+        C.byref(prm), float(max_joint_step), r.q_entry.data_ptr(), r.entry_success.data_ptr(), r.entry_iterations.data_ptr(), r.winner.data_ptr(),
+        r.err_sq.data_ptr(), r.reached.data_ptr(), r.reached_all.data_ptr(), r.q.data_ptr() if trajectory else None,
+        r.success.data_ptr() if trajectory else None, r.iterations.data_ptr() if trajectory else None, lay,
+        ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    return r
 
 
 class PickRule(enum.IntEnum):

@@ -41,6 +41,7 @@ SYMBOLS = [
     "ikgpu_line_targets", "ikgpu_dls_line_batch", "ikgpu_dls_line_workspace_bytes", "ikgpu_dls_line_kernel",
     "ikgpu_dls_goalset_batch", "ikgpu_dls_goalset_workspace_bytes", "ikgpu_dls_goalset_kernel",
     "ikgpu_path_targets", "ikgpu_dls_path_batch", "ikgpu_dls_path_workspace_bytes", "ikgpu_dls_path_kernel",
+    "ikgpu_dls_path_multistart_batch", "ikgpu_dls_path_multistart_workspace_bytes", "ikgpu_dls_path_multistart_kernel",
 ]
 MAX_PIK_LEVELS, MAX_PIK_DA = 8, 128
 
@@ -194,6 +195,13 @@ def lib():
     L.ikgpu_dls_path_workspace_bytes.restype = C.c_size_t
     L.ikgpu_dls_path_kernel.argtypes = [vp, C.POINTER(DlsParams)]
     L.ikgpu_dls_path_kernel.restype = C.c_char_p
+    L.ikgpu_dls_path_multistart_batch.argtypes = [vp, i64, i32, i64, i64, vp, vp, C.c_uint64, vp, C.POINTER(DlsParams), C.c_double, vp, vp, vp, vp,
+                                                   vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_size_t, vp]
+    L.ikgpu_dls_path_multistart_batch.restype = C.c_int
+    L.ikgpu_dls_path_multistart_workspace_bytes.argtypes = [vp, i64, i32, i64, i64, C.POINTER(DlsParams), C.c_int]
+    L.ikgpu_dls_path_multistart_workspace_bytes.restype = C.c_size_t
+    L.ikgpu_dls_path_multistart_kernel.argtypes = [vp, C.POINTER(DlsParams), i32]
+    L.ikgpu_dls_path_multistart_kernel.restype = C.c_char_p
     L.ikgpu_dls_goalset_batch.argtypes = [vp, i64, i32, i32, vp, vp, C.c_uint64, vp, C.POINTER(DlsParams), vp, vp, vp, vp, vp, vp, vp, C.c_int, vp,
                                           C.c_size_t, vp]
     L.ikgpu_dls_goalset_batch.restype = C.c_int

@@ -1117,6 +1117,42 @@ int dispatch_path_targets(const ikgpu_problem *p, int64_t B, int P, int T, const
                     "launching the path waypoint kernel");
 }
 
+// ikgpu_dls_path_batch for validated arguments, inside on_device (T >= 1): the fused launch, or the definition run as a loop in `workspace`.
+// ikgpu_dls_path_multistart_batch runs it from every start's entry result, and once more for the winner's trajectory.
+int dispatch_path(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T, const double *q0, const double *vias, const ikgpu_dls_params *params,
+                  double max_joint_step, double *q_traj, uint8_t *success, int32_t *iters, int32_t *reached, int layout, void *workspace,
+                  size_t workspace_bytes, hipStream_t st) {
+    const int64_t N = P * T;
+    if (track_is_fused(p, params)) {
+        const ikgpu::BatchIO io{B, q0, vias, q_traj, success, iters, layout};
+        ikgpu::ChainJob job{};
+        job.kind = ikgpu::ChainJob::Path;
+        job.path = ikdev::PathArgs{reached, static_cast<int>(T), static_cast<int>(P), max_joint_step};
+        return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the DLS path kernel");
+    }
+    // every other kind: the definition itself -- the waypoints, the chained calls, the met rule over flags and joint steps
+    const LineWorkspace w = line_workspace(p, B, N);
+    if (!workspace || workspace_bytes < w.total)
+        return fail(IKGPU_ERR_INVALID, "path workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                           std::to_string(w.total) + " needed (ikgpu_dls_path_workspace_bytes)");
+    char *ws = static_cast<char *>(workspace);
+    double *W = reinterpret_cast<double *>(ws + w.targets);
+    uint8_t *ok = success ? success : reinterpret_cast<uint8_t *>(ws + w.success);
+    if (const int rc = dispatch_path_targets(p, B, static_cast<int>(P), static_cast<int>(T), q0, vias, W, layout, st)) return rc;
+    const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B, t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
+    for (int64_t n = 0; n < N; ++n) {
+        const ikgpu::BatchIO io{B, n == 0 ? q0 : q_traj + (n - 1) * q_slab, W + n * t_slab, q_traj + n * q_slab, ok + n * B,
+                                iters ? iters + n * B : nullptr, layout};
+        if (const int rc = dispatch_dls(p, io, params, st)) {
+            g_last_error = "waypoint " + std::to_string(n) + ": " + g_last_error;
+            return rc;
+        }
+    }
+    if (!reached) return static_cast<int>(IKGPU_OK);
+    const ikgpu::PathReached r{B, p->host.nq, static_cast<int>(N), layout, max_joint_step, p->dev.q_in_chain, ok, q0, q_traj, reached};
+    return launched(ikgpu::launch_path_reached(r, st), "launching the path count");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1158,36 +1194,8 @@ int ikgpu_dls_path_batch(const ikgpu_problem *p, int64_t B, int64_t P, int64_t T
     if (!q0 || !vias || !q_traj) return null_argument();
     if (int rc = check_launch_size(B)) return rc;
     if (int rc = check_line_slots(p)) return rc;
-    const int64_t N = P * T;
     return on_device(p->device, stream, [&](hipStream_t st) {
-        if (track_is_fused(p, params)) {
-            const ikgpu::BatchIO io{B, q0, vias, q_traj, success, iters, layout};
-            ikgpu::ChainJob job{};
-            job.kind = ikgpu::ChainJob::Path;
-            job.path = ikdev::PathArgs{reached, static_cast<int>(T), static_cast<int>(P), max_joint_step};
-            return launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the DLS path kernel");
-        }
-        // every other kind: the definition itself -- the waypoints, the chained calls, the met rule over flags and joint steps
-        const LineWorkspace w = line_workspace(p, B, N);
-        if (!workspace || workspace_bytes < w.total)
-            return fail(IKGPU_ERR_INVALID, "path workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                               std::to_string(w.total) + " needed (ikgpu_dls_path_workspace_bytes)");
-        char *ws = static_cast<char *>(workspace);
-        double *W = reinterpret_cast<double *>(ws + w.targets);
-        uint8_t *ok = success ? success : reinterpret_cast<uint8_t *>(ws + w.success);
-        if (const int rc = dispatch_path_targets(p, B, static_cast<int>(P), static_cast<int>(T), q0, vias, W, layout, st)) return rc;
-        const int64_t q_slab = static_cast<int64_t>(p->host.nq) * B, t_slab = static_cast<int64_t>(p->host.ntasks) * 12 * B;
-        for (int64_t n = 0; n < N; ++n) {
-            const ikgpu::BatchIO io{B, n == 0 ? q0 : q_traj + (n - 1) * q_slab, W + n * t_slab, q_traj + n * q_slab, ok + n * B,
-                                    iters ? iters + n * B : nullptr, layout};
-            if (const int rc = dispatch_dls(p, io, params, st)) {
-                g_last_error = "waypoint " + std::to_string(n) + ": " + g_last_error;
-                return rc;
-            }
-        }
-        if (!reached) return static_cast<int>(IKGPU_OK);
-        const ikgpu::PathReached r{B, p->host.nq, static_cast<int>(N), layout, max_joint_step, p->dev.q_in_chain, ok, q0, q_traj, reached};
-        return launched(ikgpu::launch_path_reached(r, st), "launching the path count");
+        return dispatch_path(p, B, P, T, q0, vias, params, max_joint_step, q_traj, success, iters, reached, layout, workspace, workspace_bytes, st);
     });
 }
 
@@ -1344,6 +1352,124 @@ int ikgpu_dls_pick_batch(const ikgpu_problem *p, int64_t B, int32_t K, const dou
                                                        c_k, cost};
                               return launched(ikgpu::launch_pick_merge(m, st), "launching the pick merge");
                           });
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// The workspace of the path multi-start definition run as a loop: the multi-start loop's (start_workspace with the error), then start k's
+// count [B], ONE scratch trajectory reused by every start ([N][nq x B]; the caller's own q_traj stands in when a trajectory is asked
+// for: the winner's run goes over it last) with its flags [N][B] and iteration counts [N][B], and the path call's own workspace.
+struct PathMultistartWorkspace {
+    size_t reached, traj, success, iters, path, path_bytes, total;
+};
+PathMultistartWorkspace path_multistart_workspace(const ikgpu_problem *p, int64_t B, int64_t segments, int64_t T, const ikgpu_dls_params *params,
+                                                  bool with_trajectory) {
+    size_t end = start_workspace(p, B, /*with_error=*/true).total;
+    auto take = [&](size_t n) { const size_t at = end; end += (n + 255) / 256 * 256; return at; };
+    const size_t b = static_cast<size_t>(B), n = static_cast<size_t>(segments * T);
+    PathMultistartWorkspace w{};
+    w.reached = take(4 * b);
+    if (n > 0) {
+        if (!with_trajectory) w.traj = take(8 * static_cast<size_t>(p->host.nq) * b * n);
+        w.success = take(b * n);
+        w.iters = take(4 * b * n);
+        w.path_bytes = track_is_fused(p, params) ? 0 : line_workspace(p, B, segments * T).total;
+        w.path = take(w.path_bytes);
+    }
+    w.total = end;
+    return w;
+}
+
+// K starts, P >= 1 vias (via 0 and P - 1 segments behind it), T >= 0 waypoints per segment, (P - 1) T in a 32-bit count.
+bool path_multistart_sizes_ok(int32_t K, int64_t P, int64_t T) { return K >= 1 && K <= 64 && P >= 1 && T >= 0 && !(T > 0 && P - 1 > 0x7fffffff / T); }
+
+}  // namespace
+
+extern "C" {
+
+const char *ikgpu_dls_path_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K) {
+    if (!p || !params) return "";
+    thread_local std::string name;
+    name = variant_kernel_name(p, multistart_fused_log2(p, params, K) >= 0, "_path_multistart");
+    return name.c_str();
+}
+
+size_t ikgpu_dls_path_multistart_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, int64_t P, int64_t T, const ikgpu_dls_params *params,
+                                                 int with_trajectory) {
+    if (!p || !params || B <= 0 || !path_multistart_sizes_ok(K, P, T) || multistart_fused_log2(p, params, K) >= 0) return 0;
+    return path_multistart_workspace(p, B, P - 1, T, params, with_trajectory != 0).total;
+}
+
+int ikgpu_dls_path_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, int64_t P, int64_t T, const double *q0, const double *starts,
+                                    uint64_t seed, const double *vias, const ikgpu_dls_params *params, double max_joint_step, double *q_entry,
+                                    uint8_t *entry_success, int32_t *entry_iters, int32_t *winner, double *err_sq, int32_t *reached,
+                                    int32_t *reached_all, double *q_traj, uint8_t *success, int32_t *iters, int layout, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    if (int rc = check_problem_batch(p, B)) return rc;
+    if (int rc = check_starts(K)) return rc;
+    if (int rc = refuse_if(P < 1, "the number of via poses must be at least 1 (via 0 is the path's first pose)")) return rc;
+    if (int rc = refuse_if(T < 0, "negative number of waypoints")) return rc;
+    if (int rc = refuse_if(!path_multistart_sizes_ok(K, P, T), "too many waypoints for one call ((P - 1) x T must fit 31 bits)")) return rc;
+    if (int rc = check_layout(layout)) return rc;
+    if (int rc = check_params(params)) return rc;
+    if (!(max_joint_step >= 0.0) || !std::isfinite(max_joint_step))
+        return fail(IKGPU_ERR_INVALID, "max_joint_step must be finite and not negative (0: no joint-step rule)");
+    if (params->stop_sq_tol < 0.0 && !ikgpu::visitor_extended(*params))
+        return fail(IKGPU_ERR_INVALID, "the never-stop visitor lets no start enter the path: a path multi-start needs a stop rule (stop_sq_tol >= 0)");
+    if (B == 0) return IKGPU_OK;  // an empty batch is a no-op (its pointers may be null; the problem is not looked at)
+    if (!q0 || !vias || !q_entry) return null_argument();
+    if (int rc = check_launch_size(B, K)) return rc;
+    if (P >= 2)
+        if (int rc = check_line_slots(p)) return rc;
+    const int64_t segments = P - 1, N = segments * T;
+    if (!q_traj) success = nullptr, iters = nullptr;   // (not read without a trajectory)
+    const int log2K = multistart_fused_log2(p, params, K);
+    const PathMultistartWorkspace pw = log2K < 0 ? path_multistart_workspace(p, B, segments, T, params, q_traj != nullptr) : PathMultistartWorkspace{};
+    // (the loop's workspace is refused here, before the device is selected; run_starts checks its own part again)
+    if (log2K < 0 && (!workspace || workspace_bytes < pw.total))
+        return fail(IKGPU_ERR_INVALID, "path multi-start workspace too small: " + std::to_string(workspace ? workspace_bytes : 0) + " bytes given, " +
+                                           std::to_string(pw.total) + " needed (ikgpu_dls_path_multistart_workspace_bytes)");
+    const double *behind = vias + static_cast<int64_t>(p->host.ntasks) * 12 * B;   // slab 1: via 0 of the path call (read when N > 0 only)
+    return on_device(p->device, stream, [&](hipStream_t st) {
+        if (log2K >= 0) {
+            // the scout: K lanes per problem, no trajectory store; then the winner's trajectory, an ordinary path launch from q_entry
+            const ikgpu::BatchIO io{B, q0, vias, q_entry, entry_success, entry_iters, layout};
+            ikgpu::ChainJob job{};
+            job.kind = ikgpu::ChainJob::PathMultistart;
+            job.pms.ms = ikdev::MultistartArgs{starts, p->dev.draw, seed, winner, err_sq, log2K};
+            job.pms.reached = reached;
+            job.pms.reached_all = reached_all;
+            job.pms.T = N > 0 ? static_cast<int>(T) : 0;
+            job.pms.P = N > 0 ? static_cast<int>(segments) : 0;
+            job.pms.max_joint_step = max_joint_step;
+            if (const int rc = launched(ikgpu::launch_dls_chain(p->host, p->dev, io, job, *params, st), "launching the path multi-start DLS kernel")) return rc;
+            if (!q_traj || N == 0) return static_cast<int>(IKGPU_OK);
+            return dispatch_path(p, B, segments, T, q_entry, behind, params, max_joint_step, q_traj, success, iters, nullptr, layout, nullptr, 0, st);
+        }
+        // every other case: the definition itself -- each start's entry solve, its error, the path call from its result into the scratch
+        // trajectory, and the merge into the caller's outputs; then the path call from q_entry for the trajectory
+        char *ws = static_cast<char *>(workspace);
+        int32_t *r_k = reinterpret_cast<int32_t *>(ws + pw.reached), *it_s = reinterpret_cast<int32_t *>(ws + pw.iters);
+        double *traj = q_traj ? q_traj : reinterpret_cast<double *>(ws + pw.traj);
+        uint8_t *ok_s = reinterpret_cast<uint8_t *>(ws + pw.success);
+        const StartsCall c{B, K, q0, starts, seed, vias, params, layout, workspace, start_workspace(p, B, true).total};
+        const int rc = run_starts(p, c, "path multi-start", "ikgpu_dls_path_multistart_workspace_bytes", /*with_error=*/true, st,
+                                  [&](int k, double *q, uint8_t *ok, int32_t *it, double *e, unsigned long long *key) {
+                                      if (const int rc = dispatch_eval(p, B, q, vias, e, nullptr, layout, st)) return rc;
+                                      if (N > 0)
+                                          if (const int rc = dispatch_path(p, B, segments, T, q, behind, params, max_joint_step, traj, ok_s, it_s, r_k, layout,
+                                                                           ws + pw.path, pw.path_bytes, st))
+                                              return rc;
+                                      const ikgpu::PathMultistartMerge m{
+                                          ikgpu::MultistartMerge{B, p->host.nq, p->host.rows, layout, k, q, e, ok, it, key, q_entry, entry_success, entry_iters, winner, err_sq},
+                                          N, N > 0 ? r_k : nullptr, reached, reached_all};
+                                      return launched(ikgpu::launch_path_multistart_merge(m, st), "launching the path multi-start merge");
+                                  });
+        if (rc != IKGPU_OK || !q_traj || N == 0) return rc;
+        return dispatch_path(p, B, segments, T, q_entry, behind, params, max_joint_step, q_traj, success, iters, nullptr, layout, ws + pw.path, pw.path_bytes, st);
     });
 }
 

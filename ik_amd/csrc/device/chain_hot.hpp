@@ -881,6 +881,46 @@ IKD_FN void hot_pick_body(const ChainKernelArgs<NJ> &a, const PickArgs &pk, cons
                    [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
 }
 
+// K starts per problem, the one whose branch carries the path furthest stored -- dls_chain_path_multistart_body (chain_kernel_body.hpp:
+// the definition, the lane mapping, the scout, the pieces) with the hot program: hot_multistart_lane against via 0, then path_scout with
+// hot_path_body's start and solve.  The entry result (NJ doubles, iters, err_sq) waits in registers across the path loop.
+template <int NJ, class S, class Tab, class AnyFn>
+IKD_FN int hot_path_multistart_lane(const ChainKernelArgs<NJ> &a, const PathMultistartArgs &pm, const Tab &t, int64_t b, int k, double (&q)[NJ],
+                                    bool &success, int &iters, double &err_sq, int &reached, AnyFn any_active) {
+    hot_multistart_lane<NJ, S, false>(a, pm.ms, t, b, k, q, success, iters, err_sq, any_active);
+    IKD_PIN(err_sq);   // (formed here, not sunk behind the path loop: dls_chain_path_multistart_lane)
+    double qp[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) qp[j] = q[j];
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as the general chain kernels
+    const int n = path_scout(
+        a, pm, b, qp, success, reached,
+        [&](const double (&q0)[NJ], const double (&via)[12], LineStart &ls) { line_chain_start<S::kPrismatic != 0>(a, *(ConstDesc *)a.desc, q0, via, ls); },
+        [&](double (&qw)[NJ], const double (&oMt)[12], int &it, bool &ok, bool alive) {
+            hot_dls<NJ, S, false>(t, a.prm, qw, oMt, it, ok, any_active, alive);   // (any_active by value: a fresh count per waypoint)
+        });
+    reached = success ? reached : -1;
+    return n;
+}
+
+template <int NJ, class S, class Tab, class AnyFn, class Exchange>
+IKD_FN void hot_path_multistart_body(const ChainKernelArgs<NJ> &a, const PathMultistartArgs &pm, const Tab &t, int64_t gid, AnyFn any_active,
+                                     Exchange exchange) {
+    const int64_t prob = gid >> pm.ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << pm.ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq;
+    bool success;
+    int iters, reached;
+    (void)hot_path_multistart_lane<NJ, S>(a, pm, t, b, k, q, success, iters, err_sq, reached, any_active);
+    if (valid && pm.reached_all) pm.reached_all[static_cast<int64_t>(k) * a.B + b] = reached;
+    const int win = multistart_select(pm.ms.log2K, path_multistart_key(pm, success, reached, err_sq), k, exchange);
+    if (valid && win == k)
+        path_multistart_store(a, pm, b, k, q, success, iters, err_sq, reached,
+                              [&](const double *src, bool stepped) { hot_pass_through_from(a, src, a.q_out, b, stepped); });
+}
+
 // G goals and K starts per problem, the best candidate stored -- dls_chain_goalset_body (chain_kernel_body.hpp: the definition, the lane
 // mapping, the pieces) with the hot program: hot_multistart_lane with the target taken from slab g of the goals.
 template <int NJ, class S, bool NEVERSTOP, class Tab, class AnyFn>
@@ -1036,6 +1076,14 @@ __device__ __forceinline__ void hot_pick_entry(const ChainKernelArgs<NJ> &a, con
     IKD_HOT_LUT_DECLARE(tv);
     hot_park_table<NJ, S>(t, tv);
     hot_pick_body<NJ, S>(a, pk, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
+}
+
+template <int NJ, class S>
+__device__ __forceinline__ void hot_path_multistart_entry(const ChainKernelArgs<NJ> &a, const HotTable &t, const PathMultistartArgs &pm) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    IKD_HOT_LUT_DECLARE(tv);
+    hot_park_table<NJ, S>(t, tv);
+    hot_path_multistart_body<NJ, S>(a, pm, tv, gid, KeepGoing{0, 0, 0}, MultistartShuffle{});
 }
 
 template <int NJ, class S, bool NEVERSTOP>

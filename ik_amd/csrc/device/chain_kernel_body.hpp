@@ -522,6 +522,106 @@ IKD_FN void dls_chain_pick_body(const ChainKernelArgs<NJ> &a, const PickArgs &pk
         pick_store(a, pk, b, k, q, success, iters, err_sq, cost, [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
 }
 
+// ---- path multi-start: K starts per problem in one launch, the one whose branch carries the path furthest stored (include/ikgpu.h
+// ikgpu_dls_path_multistart_batch) -------------------------------------------------------------------------------------------------------
+// Defined through the K single solves of the multi-start call against via 0 (a.targets' slab 0: the same starts, the same lane mapping,
+// the same error) and, from each result that met the stop rule, the path call through the P slabs behind via 0 (dls_chain_path_body
+// with q0 = that result: segment 0 runs from the frame's pose there).  The key orders (entered, P T - reached | error, k): pick_key.
+// The SCOUT: a lane follows the path with no trajectory store at all -- chain_dls, alive, path_jumped and the via prefetch in the path
+// body's order, so `reached` holds that call's bits -- while its entry result (NJ doubles, iters, err_sq) waits in registers; a lane
+// whose entry failed is dead from the start and the wave leaves once none of its lanes is alive.  The winner's trajectory is a second,
+// ordinary path launch from q_entry: 1 / K of the lanes, one buffer.
+
+// The path loop of dls_chain_path_body / hot_path_body from q without its stores: start(q, via, ls) is the build's line_chain_start,
+// solve(q, oMt, iters, success, alive) its loop.  q is left at the last result; returns the waypoints the lane's wave went through.
+template <int NJ, class Start, class Solve>
+IKD_FN int path_scout(const ChainKernelArgs<NJ> &a, const PathMultistartArgs &pm, int64_t b, double (&q)[NJ], bool alive, int &reached, Start start,
+                      Solve solve) {
+    const int64_t t_slab = 12 * a.B;
+    const double *vias = a.targets + t_slab;   // slab s of the path call
+    reached = 0;
+    int n = 0;
+    if (pm.P < 1 || pm.T < 1) return n;   // (wave-uniform: no slab behind via 0 is read)
+    double q_prev[NJ], via[12], next[12];
+    load_target_raw(a, vias, b, via);
+    LineStart ls;
+    start(q, via, ls);
+    for (int s = 0; s < pm.P && IKD_ANY(alive); ++s) {
+        for (int k = 0; k < pm.T && IKD_ANY(alive); ++k, ++n) {
+            double t[12], oMt[12];
+            line_waypoint(ls, via, k, pm.T, t);
+            compose_target(a, t, oMt);
+            const bool turn = k + 1 == pm.T && s + 1 < pm.P;   // the last waypoint of a segment that has a successor
+            if (turn) load_target_raw(a, vias + (s + 1) * t_slab, b, next);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) q_prev[j] = q[j];
+            int iters;
+            bool success;
+            solve(q, oMt, iters, success, alive);
+            if (turn) {
+                line_start_from_pose(via, next, ls);
+#pragma unroll
+                for (int c = 0; c < 12; ++c) via[c] = next[c];
+            }
+            alive = alive && success && !path_jumped<NJ>(q, q_prev, pm.max_joint_step);
+            reached += alive ? 1 : 0;
+        }
+    }
+    return n;
+}
+
+// What a start is ranked by: pick_key with the waypoints it did NOT reach as the cost (an exact small integer in a double).
+IKD_FN unsigned long long path_multistart_key(const PathMultistartArgs &pm, bool success, int reached, double err_sq) {
+    const int64_t N = static_cast<int64_t>(pm.P) * pm.T;
+    return pick_key(success, static_cast<double>(N - (success ? reached : 0)), err_sq);
+}
+
+// One start: the multi-start lane against via 0 (dls_chain_multistart_lane: the same statements), then the scout from a copy of its
+// result.  reached = -1 for a start whose entry failed.
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
+IKD_FN int dls_chain_path_multistart_lane(const ChainKernelArgs<NJ> &a, const PathMultistartArgs &pm, const Desc &d, int64_t b, int k,
+                                          double (&q)[NJ], bool &success, int &iters, double &err_sq, int &reached, AnyFn any_active) {
+    dls_chain_multistart_lane<NJ, KT, SMASK>(a, pm.ms, d, b, k, q, success, iters, err_sq, any_active);
+    IKD_PIN(err_sq);   // the error is formed HERE: sunk to its use behind the path loop, the trailing evaluation's inputs would wait with it
+    double qp[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) qp[j] = q[j];
+    const int n = path_scout(
+        a, pm, b, qp, success, reached,
+        [&](const double (&q0)[NJ], const double (&via)[12], LineStart &ls) { line_chain_start<ReadsKinds<SMASK>::value>(a, d, q0, via, ls); },
+        [&](double (&qw)[NJ], const double (&oMt)[12], int &it, bool &ok, bool alive) {
+            chain_dls<NJ, KT, SMASK>(d, a.prm, qw, oMt, it, ok, any_active, alive);   // (any_active by value: a fresh count per waypoint)
+        });
+    reached = success ? reached : -1;
+    return n;
+}
+
+// The winning lane's stores: multistart_store (q_entry over all nq entries, the flags, winner, err_sq) and the winner's count.
+template <int NJ, class Pass>
+IKD_FN void path_multistart_store(const ChainKernelArgs<NJ> &a, const PathMultistartArgs &pm, int64_t b, int k, const double (&q)[NJ], bool success,
+                                  int iters, double err_sq, int reached, Pass pass) {
+    multistart_store(a, pm.ms, b, k, q, success, iters, err_sq, pass);
+    if (pm.reached) pm.reached[b] = success ? reached : 0;
+}
+
+template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn, class Exchange>
+IKD_FN void dls_chain_path_multistart_body(const ChainKernelArgs<NJ> &a, const PathMultistartArgs &pm, const Desc &d, int64_t gid, AnyFn any_active,
+                                           Exchange exchange) {
+    const int64_t prob = gid >> pm.ms.log2K;
+    const int k = static_cast<int>(gid & ((int64_t{1} << pm.ms.log2K) - 1));
+    const bool valid = prob < a.B;
+    const int64_t b = valid ? prob : a.B - 1;  // tail lanes (whole groups) shadow the last problem and store nothing
+    double q[NJ], err_sq;
+    bool success;
+    int iters, reached;
+    (void)dls_chain_path_multistart_lane<NJ, KT, SMASK>(a, pm, d, b, k, q, success, iters, err_sq, reached, any_active);
+    if (valid && pm.reached_all) pm.reached_all[static_cast<int64_t>(k) * a.B + b] = reached;
+    const int win = multistart_select(pm.ms.log2K, path_multistart_key(pm, success, reached, err_sq), k, exchange);
+    if (valid && win == k)
+        path_multistart_store(a, pm, b, k, q, success, iters, err_sq, reached,
+                              [&](const double *src, bool stepped) { chain_pass_through_from(a, src, b, stepped); });
+}
+
 // ---- goal set: G alternative goals and K starts per problem in one launch, the best candidate stored (include/ikgpu.h
 // ikgpu_dls_goalset_batch) ------------------------------------------------------------------------------------------------------------
 // Defined through the G x K single solves "start k against goal g" (the starts are the multi-start call's and do not depend on the goal;

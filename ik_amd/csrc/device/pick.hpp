@@ -26,6 +26,17 @@ struct PickArgs {
     int rule;
 };
 
+// What a path multi-start kernel takes besides the single solve's arguments (include/ikgpu.h ikgpu_dls_path_multistart_batch): the K
+// starts solve against via 0 (a.targets' slab 0), every start that entered follows the P segments of T waypoints through the slabs
+// behind it, and the start that gets furthest is stored -- pick_key with cost = P T - reached.
+struct PathMultistartArgs {
+    MultistartArgs ms;          // the starts, the draw, winner / err_sq and log2 K: the multi-start kernel's
+    int32_t *reached;           // [B] or null: the winner's count, 0 when its entry failed
+    int32_t *reached_all;       // [K][B] or null: every start's count, -1 where the entry failed
+    int T, P;                   // waypoints per segment >= 0, segments behind via 0 >= 0
+    double max_joint_step;      // the path kernels' (line.hpp path_jumped)
+};
+
 // finite, read from the bits: the hot kernels are built with -fno-honor-nans / -fno-honor-infinities
 IKD_FN bool pick_finite(double x) { return (multistart_bits(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 

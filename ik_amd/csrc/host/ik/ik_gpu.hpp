@@ -805,6 +805,37 @@ inline void dls_multistart_device(InverseKinematicsProblem &problem, std::int64_
         throw std::runtime_error(ikgpu_last_error());
 }
 
+// The start whose IK branch carries the path, on DEVICE buffers (include/ikgpu.h ikgpu_dls_path_multistart_batch): each of
+// dls_multistart_device's K starts solves vias' slab 0, the path's first pose (ik::dls is a local method: ik/ik/dls.cpp:10, :73;
+// ik/ik/dls.hpp:27); every start that met the stop rule (ik/ik/dls.cpp:61-64,76-77) is followed along dls_path_device from its result
+// through slabs 1 .. P-1 (the caller's sequence, ik_ros/src/cassie.cpp:92-113); the one that gets furthest wins, a tie goes to the lowest
+// index, and with no start entered the smallest error wins.  vias [P][ntasks][12][B]; Q_entry [nq][B], entry_success / entry_iterations
+// / winner / err_sq / reached [B], reached_all [K][B] (-1: the entry failed), Q [(P-1) T][nq][B] or null (no trajectory) with success /
+// iterations [(P-1) T][B]; everything but Q_entry may be null.  workspace: device memory of dls_path_multistart_workspace_bytes() bytes (0 for
+// a chain problem with K in {2, 4, .., 64}: a scout launch and the winner's path launch).  Asynchronous on `stream`.
+inline std::size_t dls_path_multistart_workspace_bytes(InverseKinematicsProblem &problem, std::int64_t B, int K, std::int64_t P, std::int64_t T,
+                                                       dls_data &data, bool with_trajectory = true,
+                                                       const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                                       const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    return ikgpu_dls_path_multistart_workspace_bytes(data.handle(), B, K, P, T, &prm, with_trajectory ? 1 : 0);
+}
+inline void dls_path_multistart_device(InverseKinematicsProblem &problem, std::int64_t B, int K, std::int64_t P, std::int64_t T, const number_t *Q0,
+                                       const number_t *starts, std::uint64_t seed, const number_t *vias, number_t max_joint_step, dls_data &data,
+                                       number_t *Q_entry, std::uint8_t *entry_success, std::int32_t *entry_iterations, std::int32_t *winner,
+                                       number_t *err_sq, std::int32_t *reached, std::int32_t *reached_all, number_t *Q, std::uint8_t *success,
+                                       std::int32_t *iterations, void *workspace, std::size_t workspace_bytes, void *stream,
+                                       const inverse_kinematics_visitor &visitor = inverse_kinematics_visitor(),
+                                       const dls_parameters &p = dls_parameters()) {
+    data.bind(problem);
+    const ikgpu_dls_params prm = detail::to_abi(visitor, p);
+    if (ikgpu_dls_path_multistart_batch(data.handle(), B, K, P, T, Q0, starts, seed, vias, &prm, max_joint_step, Q_entry, entry_success,
+                                        entry_iterations, winner, err_sq, reached, reached_all, Q, success, iterations, IKGPU_SOA, workspace,
+                                        workspace_bytes, stream) != IKGPU_OK)
+        throw std::runtime_error(ikgpu_last_error());
+}
+
 // Among K starts per problem on DEVICE buffers (dls_multistart_device's starts), the one that met the stop rule with the smallest cost
 // under `rule`: the configuration closest to q_ref (null: Q0), the one furthest from its joint limits, or the best-conditioned one
 // (include/ikgpu.h ikgpu_dls_pick_batch; ik::dls is a local method: ik/ik/dls.cpp:10, :73).  A tie goes to the lowest index; when no start

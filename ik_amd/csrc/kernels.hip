@@ -262,6 +262,15 @@ __global__ __launch_bounds__(kBlock) void dls_chain_pick_kernel(const ChainKerne
     ikdev::dls_chain_pick_body<NJ, KT, SMASK>(a, pk, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
 }
 
+// K starts per problem in one launch against via 0, each scouting the path behind it, the one that gets furthest stored
+// (device/chain_kernel_body.hpp dls_chain_path_multistart_body): the general build's path multi-start kernel.
+template <int NJ, int KT, int SMASK>
+__global__ __launch_bounds__(kBlock) void dls_chain_path_multistart_kernel(const ChainKernelArgs<NJ> a, const ikdev::PathMultistartArgs pm) {
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+    ikdev::dls_chain_path_multistart_body<NJ, KT, SMASK>(a, pm, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
+}
+
 // K starts per problem in one launch, the distinct converged ones stored (device/chain_kernel_body.hpp dls_chain_solutions_body): the
 // general build's solution-set kernel.
 template <int NJ, int KT, int SMASK>
@@ -381,6 +390,29 @@ __global__ __launch_bounds__(256) void pick_merge(const PickMerge p) {
     if (m.winner) m.winner[b] = m.k;
     if (m.err_sq) m.err_sq[b] = err;
     if (p.cost_out) p.cost_out[b] = p.cost[b];
+}
+
+__global__ __launch_bounds__(256) void path_multistart_merge(const PathMultistartMerge p) {
+    const MultistartMerge &m = p.m;
+    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= m.B) return;
+    double err = 0.0;
+    for (int r = 0; r < m.M; ++r) {
+        const double e = m.e[ikdev::at(m.layout, m.B, m.M, r, b)];
+        err = ikdev::dfma(e, e, err);
+    }
+    const bool entered = m.success[b] != 0;
+    const int reached = !entered ? -1 : p.reached_k ? p.reached_k[b] : 0;
+    if (p.reached_all) p.reached_all[static_cast<int64_t>(m.k) * m.B + b] = reached;
+    const unsigned long long key = ikdev::pick_key(entered, static_cast<double>(p.N - (entered ? reached : 0)), err);
+    if (m.k > 0 && !(key < m.key[b])) return;   // (a tie keeps the lower index)
+    m.key[b] = key;
+    for (int i = 0; i < m.nq; ++i) m.q_out[ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
+    if (m.success_out) m.success_out[b] = m.success[b];
+    if (m.iters_out) m.iters_out[b] = m.iters[b];
+    if (m.winner) m.winner[b] = m.k;
+    if (m.err_sq) m.err_sq[b] = err;
+    if (p.reached_out) p.reached_out[b] = entered ? reached : 0;
 }
 
 __global__ __launch_bounds__(256) void goalset_reachable_kernel(int64_t B, bool first, const uint8_t *success, uint8_t *reachable) {
@@ -506,9 +538,12 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
         constexpr int SM = decltype(smask)::value;
         if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
         const dim3 grid = grid_for(job.lanes(io.B));
-        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line || job.kind == ChainJob::Path || job.kind == ChainJob::Pick) && prm.stop_sq_tol < 0.0)
+        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line || job.kind == ChainJob::Path || job.kind == ChainJob::Pick ||
+             job.kind == ChainJob::PathMultistart) && prm.stop_sq_tol < 0.0)
             return hipErrorInvalidValue;
-        if (job.kind == ChainJob::Pick) hipLaunchKernelGGL((dls_chain_pick_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.pick);
+        if (job.kind == ChainJob::PathMultistart)
+            hipLaunchKernelGGL((dls_chain_path_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.pms);
+        else if (job.kind == ChainJob::Pick) hipLaunchKernelGGL((dls_chain_pick_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.pick);
         else if (job.kind == ChainJob::Path) hipLaunchKernelGGL((dls_chain_path_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.path);
         else if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
         else if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
@@ -765,6 +800,11 @@ hipError_t launch_pick_cost(const PickCost &c, hipStream_t stream) {
 
 hipError_t launch_pick_merge(const PickMerge &m, hipStream_t stream) {
     hipLaunchKernelGGL(pick_merge, dim3(static_cast<unsigned>((m.m.B + 255) / 256)), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_multistart_merge(const PathMultistartMerge &m, hipStream_t stream) {
+    hipLaunchKernelGGL(path_multistart_merge, dim3(static_cast<unsigned>((m.m.B + 255) / 256)), dim3(256), 0, stream, m);
     return hipGetLastError();
 }
 

@@ -93,10 +93,13 @@ struct BatchIO {
 //               path.reached counts the ones before it.  Needs a stop rule, as Line.
 //   Pick:       the Multistart lanes (pick.ms), the start that met the stop rule with the smallest cost stored (ikgpu_dls_pick_batch;
 //               dls_chain_pick_body, hot_pick_body).  Needs a stop rule, as Solutions.
-// Track, Multistart, Solutions, Line, Goalset, Path and Pick are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
+//   PathMultistart: the Multistart lanes (pms.ms) against via 0 = `io.targets`' slab 0, every start that entered then SCOUTS the path
+//               through the pms.P slabs behind it without storing a trajectory, and the start that gets furthest is stored with its
+//               count (ikgpu_dls_path_multistart_batch; dls_chain_path_multistart_body, hot_path_multistart_body).  Needs a stop rule.
+// Track, Multistart, Solutions, Line, Goalset, Path, Pick and PathMultistart are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
 // capturable.
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset, Path, Pick } kind = Solve;
+    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset, Path, Pick, PathMultistart } kind = Solve;
     int T = 0;                     // Track: the number of waypoints
     ikdev::MultistartArgs ms{};    // Multistart
     ikdev::SolutionsArgs sol{};    // Solutions
@@ -104,8 +107,10 @@ struct ChainJob {
     ikdev::GoalsetArgs goal{};     // Goalset
     ikdev::PathArgs path{};        // Path
     ikdev::PickArgs pick{};        // Pick
+    ikdev::PathMultistartArgs pms{};   // PathMultistart
     int64_t lanes(int64_t B) const {   // one lane per problem, per start, or per (goal, start)
-        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : kind == Pick ? B << pick.ms.log2K : B;
+        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : kind == Pick ? B << pick.ms.log2K
+               : kind == PathMultistart ? B << pms.ms.log2K : B;
     }
 };
 
@@ -184,6 +189,17 @@ struct PickMerge {
     double *cost_out;               // [B] or null
 };
 hipError_t launch_pick_merge(const PickMerge &m, hipStream_t stream);
+// One step of the path multi-start definition run as a loop (ikgpu_dls_path_multistart_batch): launch_multistart_merge under
+// pick_key(success, N - reached_k, err), reached_k = the path call's count from start k's result (`reached_k`, null when N = 0: zero),
+// -1 for a start whose entry failed; reached_all's row k is written for every problem, reached_out for the problems start k takes.
+struct PathMultistartMerge {
+    MultistartMerge m;
+    int64_t N;
+    const int32_t *reached_k;       // [B] or null
+    int32_t *reached_out;           // [B] or null
+    int32_t *reached_all;           // [K][B] or null
+};
+hipError_t launch_path_multistart_merge(const PathMultistartMerge &m, hipStream_t stream);
 // One step of the goal-set definition run as a loop: reachable[b] = (first ? 0 : reachable[b]) | success[b], over the starts of one goal.
 hipError_t launch_goalset_reachable(int64_t B, bool first, const uint8_t *success, uint8_t *reachable, hipStream_t stream);
 // ... and its last: the winning candidate j = winner[b] (which may be `goal` or `start` itself) into goal[b] = j / K, start[b] = j % K;

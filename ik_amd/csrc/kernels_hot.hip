@@ -64,6 +64,15 @@ __global__ __launch_bounds__(kBlock) void dls_chain_hot_pick_kernel(const ChainK
     ikdev::hot_pick_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pk);
 }
 
+// K starts per problem in one launch against via 0, each scouting the path behind it without a trajectory store, the one that gets
+// furthest stored (device/chain_hot.hpp hot_path_multistart_body; include/ikgpu.h ikgpu_dls_path_multistart_batch): the multi-start
+// kernel's lane mapping.  Stop rule only; lock-step per solve; no LDS beyond the sin / cos table, no queue slot, no allocation.
+template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
+__global__ __launch_bounds__(kBlock) void dls_chain_hot_path_multistart_kernel(const ChainKernelArgs<NJ> a, const HotTable t,
+                                                                               const ikdev::PathMultistartArgs pm) {
+    ikdev::hot_path_multistart_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pm);
+}
+
 // G goals and K starts per problem in one launch, the best candidate stored (device/chain_hot.hpp hot_goalset_body; include/ikgpu.h
 // ikgpu_dls_goalset_batch): lane gid serves problem gid / (G K) with goal (gid / K) % G and start gid % K.  Lock-step; no LDS, no queue
 // slot, no allocation.
@@ -158,6 +167,9 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
         } else if (job.kind == ChainJob::Pick) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
             else hipLaunchKernelGGL((dls_chain_hot_pick_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.pick);
+        } else if (job.kind == ChainJob::PathMultistart) {
+            if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
+            else hipLaunchKernelGGL((dls_chain_hot_path_multistart_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.pms);
         } else if (job.kind == ChainJob::Line) {
             if constexpr (NEVER) return hipErrorInvalidValue;   // (nothing is ever reached without a stop rule: refused likewise)
             else hipLaunchKernelGGL((dls_chain_hot_line_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.line);

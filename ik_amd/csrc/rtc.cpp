@@ -131,7 +131,7 @@ const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fn
 //       ikdev::<entry><NJ, S<flag>>(a, t<args>);
 //   }
 enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotSolutionsStop, kHotLineStop,
-       kHotGoalsetNever, kHotGoalsetStop, kHotPathStop, kHotPickStop, kHotEntries };
+       kHotGoalsetNever, kHotGoalsetStop, kHotPathStop, kHotPickStop, kHotPathMultistartStop, kHotEntries };
 struct HotEntry {
     const char *name, *params, *entry, *flag, *args;
     bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
@@ -157,6 +157,9 @@ const HotEntry kHotEntryTable[kHotEntries] = {
     {"ikgpu_hot_path_stop", ", const ikdev::PathArgs pa", "hot_path_entry", "", ", pa", false},
     // K starts per problem in one launch, the converged one with the smallest cost stored (ikgpu_dls_pick_batch): a stop rule always, so one entry
     {"ikgpu_hot_pick_stop", ", const ikdev::PickArgs pk", "hot_pick_entry", "", ", pk", false},
+    // K starts per problem against via 0, each scouting the path behind it, the one that gets furthest stored
+    // (ikgpu_dls_path_multistart_batch): a stop rule always, so one entry
+    {"ikgpu_hot_path_multistart_stop", ", const ikdev::PathMultistartArgs pm", "hot_path_multistart_entry", "", ", pm", false},
 };
 // The row of a job, or -1: a solution-set, line or path job has no never-stop entry.
 int hot_entry(ChainJob::Kind kind, bool never) {
@@ -164,6 +167,7 @@ int hot_entry(ChainJob::Kind kind, bool never) {
     if (kind == ChainJob::Line) return never ? -1 : kHotLineStop;
     if (kind == ChainJob::Path) return never ? -1 : kHotPathStop;
     if (kind == ChainJob::Pick) return never ? -1 : kHotPickStop;
+    if (kind == ChainJob::PathMultistart) return never ? -1 : kHotPathMultistartStop;
     if (kind == ChainJob::Goalset) return never ? kHotGoalsetNever : kHotGoalsetStop;
     static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
     return first[kind] + (never ? 0 : 1);
@@ -592,17 +596,20 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
             ikdev::GoalsetArgs ga;
             ikdev::PathArgs pa;
             ikdev::PickArgs pk;
+            ikdev::PathMultistartArgs pm;
         } tail;
     } args{};
     constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
     static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8 &&
                       alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8 && alignof(ikdev::GoalsetArgs) == 8 &&
-                      alignof(ikdev::PathArgs) == 8 && alignof(ikdev::PickArgs) == 8, "argument layout");
+                      alignof(ikdev::PathArgs) == 8 && alignof(ikdev::PickArgs) == 8 && alignof(ikdev::PathMultistartArgs) == 8,
+                  "argument layout");
     constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
                      kBytesTrack = offsetof(Args, tail.T) + sizeof(int),
                      kBytesMultistart = offsetof(Args, tail) + sizeof(ikdev::MultistartArgs), kBytesSolutions = offsetof(Args, tail) + sizeof(ikdev::SolutionsArgs),
                      kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs), kBytesGoalset = offsetof(Args, tail) + sizeof(ikdev::GoalsetArgs),
-                     kBytesPath = offsetof(Args, tail) + sizeof(ikdev::PathArgs), kBytesPick = offsetof(Args, tail) + sizeof(ikdev::PickArgs);
+                     kBytesPath = offsetof(Args, tail) + sizeof(ikdev::PathArgs), kBytesPick = offsetof(Args, tail) + sizeof(ikdev::PickArgs),
+                     kBytesPathMultistart = offsetof(Args, tail) + sizeof(ikdev::PathMultistartArgs);
     static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
     static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
     static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
@@ -612,6 +619,7 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     static_assert(kBytesGoalset == kHead + sizeof(ikdev::GoalsetArgs), "goal set: the whole of (a, t, ga)");
     static_assert(kBytesPath == kHead + sizeof(ikdev::PathArgs), "path: the whole of (a, t, pa)");
     static_assert(kBytesPick == kHead + sizeof(ikdev::PickArgs), "pick: the whole of (a, t, pk)");
+    static_assert(kBytesPathMultistart == kHead + sizeof(ikdev::PathMultistartArgs), "path multi-start: the whole of (a, t, pm)");
     ikdev::ChainKernelArgs<NJ> &a = args.a;
     fill_chain_kernel_args(a, ph, dt);
     fill_solve_args(a, io, prm);
@@ -641,6 +649,10 @@ hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const Bat
     if (job.kind == ChainJob::Pick) {
         args.tail.pk = job.pick;
         return launch(entry, waves, kBytesPick);
+    }
+    if (job.kind == ChainJob::PathMultistart) {
+        args.tail.pm = job.pms;
+        return launch(entry, waves, kBytesPathMultistart);
     }
     if (job.kind == ChainJob::Goalset) {
         args.tail.ga = job.goal;

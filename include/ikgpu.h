@@ -459,6 +459,54 @@ size_t ikgpu_dls_path_workspace_bytes(const ikgpu_problem *p, int64_t B, int64_t
  * waypoint.  The string belongs to the calling thread and lasts until its next call. */
 const char *ikgpu_dls_path_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params);
 
+/* ---- path multi-start: the start whose IK branch carries the path.  The robot is not on the path yet: it may move freely in joint space
+ * to the path's first pose, and WHICH solution of that pose it takes decides how far the Cartesian path can be followed without a
+ * joint jump.  ik::dls is a local method (reference ik/ik/dls.cpp:10, :73; ik/ik/dls.hpp:27), so the K starts of
+ * ikgpu_dls_multistart_batch are tried -- the same starts, the same draw, the same err_k, word for word -- and each one that reaches the
+ * first pose is followed along the path (the caller's sequence, ik_ros/src/cassie.cpp:92-113, as ikgpu_dls_path_batch defines it).
+ *   vias [P][ntasks x 12 x B]  P >= 1 slabs; via 0 is the path's first pose; N = (P-1)*T waypoints lie behind it.
+ * Candidate k: r_k = (q_k, success_k, iters_k) is what ikgpu_dls_solve_batch writes from start k with targets = via 0 (the stop test
+ * and failure report of ik/ik/dls.cpp:61-64,76-77).  If success_k, reached_k is what ikgpu_dls_path_batch(q0 = q_k, vias = slabs
+ * 1 .. P-1, P-1, T, max_joint_step) writes as `reached`: segment 0 of that path runs from the frame's pose at q_k, so the joint-step
+ * rule (over the entries with ikgpu_problem_support = 1) is measured from q_k.  If the entry failed, reached_k counts as -1.  N = 0:
+ * reached_k = 0 for every start that entered.
+ * The winner is the k with the smallest key (success_k ? 0 : 1, success_k ? N - reached_k : err_k, k): among the starts that entered,
+ * the one that gets furthest; a tie goes to the lowest index, so a warm start (start 0 = q0) keeps its branch when it is as good as
+ * any; when no start entered, the smallest error, as in multi-start; a non-finite error ranks as +infinity.
+ *   q_entry [nq x B], entry_success [B], entry_iters [B]   r_winner, bit for bit over all nq entries
+ *   winner [B] the winning start, err_sq [B] err_winner, reached [B] reached_winner (0 when the winner's entry failed)
+ *   reached_all [K][B]   reached_k, -1 for a failed entry
+ *   q_traj [(P-1)*T][nq x B], success, iters [(P-1)*T][B]   (q_traj NULL: no trajectory; success / iters are then not read) for a problem
+ *   with entry_success = 1, slabs n <= min(reached, N-1) are written and bit-identical to ikgpu_dls_path_batch(q0 = q_entry, slabs
+ *   1 .., P-1, T, max_joint_step); the failing slab carries the solve's own flag; later slabs, and every slab of a problem with
+ *   entry_success = 0, are unspecified.
+ * Every output except q_entry may be NULL.  q_entry and q_traj must overlap neither each other nor any input.  IKGPU_ERR_INVALID: K
+ * outside 1 .. 64, P < 1, T < 0, (P-1)*T > 0x7fffffff, max_joint_step not finite or negative, a workspace that is too short, the
+ * never-stop visitor (no start ever enters).  IKGPU_ERR_UNSUPPORTED: the slot restrictions of ikgpu_path_targets, when P >= 2.  B == 0
+ * is a no-op.  P = 1 is ikgpu_dls_multistart_batch on via 0, bit for bit, with reached = 0.
+ * A chain problem under the reference's visitor with K in {2, 4, .., 64} takes TWO launches and no workspace.  The scout
+ * (`dls_chain_path_multistart<...>`): the multi-start lane mapping (lane gid serves problem gid / K from start gid % K); a lane solves
+ * the entry, keeps its result in registers and follows the path WITHOUT storing a trajectory; a lane whose entry failed is dead from
+ * the start and the wave leaves once none of its lanes is alive; then every lane stores its reached_all entry, the K lanes select and
+ * the winner alone stores.  Then, with q_traj, the ordinary `dls_chain_path<...>` launch from q_entry on the same stream: 1 / K of the
+ * scout's lanes, ONE trajectory buffer instead of K.  Every other case -- tree, generic and static-program problems, derived visitors,
+ * K = 1, K not a power of two -- runs the definition from inside the call, start after start, in `workspace` (DEVICE memory of at
+ * least ikgpu_dls_path_multistart_workspace_bytes bytes: one scratch trajectory reused per start, or q_traj itself when given, and the
+ * per-start results); ikgpu_last_error names the failing start or waypoint. */
+int ikgpu_dls_path_multistart_batch(const ikgpu_problem *p, int64_t B, int32_t K, int64_t P, int64_t T, const double *q0,
+                                    const double *starts /* [K-1][nq x B] or NULL: generated from seed */, uint64_t seed, const double *vias,
+                                    const ikgpu_dls_params *params, double max_joint_step, double *q_entry, uint8_t *entry_success,
+                                    int32_t *entry_iters, int32_t *winner, double *err_sq, int32_t *reached, int32_t *reached_all /* [K][B] */,
+                                    double *q_traj /* [(P-1)*T][nq x B], or NULL: no trajectory */, uint8_t *success, int32_t *iters,
+                                    int layout /* ikgpu_layout */, void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of `workspace` ikgpu_dls_path_multistart_batch needs for these arguments (with_trajectory: q_traj != NULL): 0 for the two launches. */
+size_t ikgpu_dls_path_multistart_workspace_bytes(const ikgpu_problem *p, int64_t B, int32_t K, int64_t P, int64_t T,
+                                                 const ikgpu_dls_params *params, int with_trajectory);
+/* Name of what ikgpu_dls_path_multistart_batch runs with these parameters: `dls_chain_path_multistart<NJ=6,full,hot>` (or hot-rtc /
+ * general: the build ikgpu_problem_kernel reports) for the scout, `loop(<ikgpu_problem_kernel's name>)` for the definition run start
+ * after start.  The string belongs to the calling thread and lasts until its next call. */
+const char *ikgpu_dls_path_multistart_kernel(const ikgpu_problem *p, const ikgpu_dls_params *params, int32_t K);
+
 /* ---- goal set: reach ANY of G alternative goal poses per problem -- G grasp candidates on an object, G footholds, G docking poses --
  * from K starts, and learn which goals are reachable at all.  ik::dls is a local method (reference ik/ik/dls.cpp:10 "todo - if limited
  * convergence, try random walk"; dls.cpp:73 "If issues, perform random restart"; dls_parameters::random_restart, ik/ik/dls.hpp:27, is a
