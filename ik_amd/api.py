@@ -21,6 +21,7 @@ The C++ mirror of the same classes lives in ik_amd/csrc/host/ik/.  No arithmetic
 import collections
 import ctypes as C
 import enum
+import math
 
 import numpy as np
 
@@ -468,39 +469,6 @@ class dls_data:
             pass
 
 
-def plan(problem):
-    """Name of the kernel specialisation the problem maps to (host-only; raises IkgpuError when the
-    shape has no device kernel)."""
-    arr = _task_table(problem)
-    cons, ncons = _constraint_table(problem)
-    buf = C.create_string_buffer(160)
-    capi.check(capi.lib().ikgpu_problem_plan_constrained(problem.model()._h, arr, len(arr), cons, ncons, buf, len(buf)))
-    return buf.value.decode()
-
-
-def tree_build(problem, visitor=None, p=None, pik_levels=0):
-    """Which compile-time build of the tree kernel a solve of the problem launches (host-only, include/ikgpu.h
-    ikgpu_dls_tree_build_plan): "<build>,<folded|unfolded>,<extras>,refill=<twin>", or "" when the solve does not run on the tree
-    kernel.  pik_levels: 0 for dls / dls_batch, 1 or 2 for pik with that many levels."""
-    arr = _task_table(problem)
-    cons, ncons = _constraint_table(problem)
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    buf = C.create_string_buffer(160)
-    capi.check(capi.lib().ikgpu_dls_tree_build_plan(problem.model()._h, arr, len(arr), cons, ncons, C.byref(prm), pik_levels, buf, len(buf)))
-    return buf.value.decode()
-
-
-def precompile(problem):
-    """Compile ahead of time (host-only, no device) what dls_data(problem) would compile at run time -- the structure-specialised
-    chain kernel of a chain without a pre-built instantiation -- into the on-disk cache; returns the kernel name.  Raises
-    IkgpuError (UNSUPPORTED) with the compiler's log when the compilation fails (the problem then runs on the general build)."""
-    arr = _task_table(problem)
-    cons, ncons = _constraint_table(problem)
-    buf = C.create_string_buffer(160)
-    capi.check(capi.lib().ikgpu_problem_precompile(problem.model()._h, arr, len(arr), cons, ncons, buf, len(buf)))
-    return buf.value.decode()
-
-
 def _params(visitor, p):
     lt = tuple(getattr(visitor, "level_tolerances", ()))
     if len(lt) > capi.MAX_VISITOR_LEVELS:
@@ -508,6 +476,148 @@ def _params(visitor, p):
     return capi.DlsParams(int(p.max_iterations), float(p.damping), float(p.step_length), float(visitor.tolerance),
                           float(getattr(visitor, "step_tolerance", 0.0)), len(lt),
                           (C.c_double * capi.MAX_VISITOR_LEVELS)(*(list(lt) + [0.0] * (capi.MAX_VISITOR_LEVELS - len(lt)))))
+
+
+def _describe(fn, problem, *extra):
+    """The string a host-only C entry writes about (model, task table, constraint table, *extra)."""
+    arr = _task_table(problem)
+    cons, ncons = _constraint_table(problem)
+    buf = C.create_string_buffer(160)
+    capi.check(fn(problem.model()._h, arr, len(arr), cons, ncons, *extra, buf, len(buf)))
+    return buf.value.decode()
+
+
+def plan(problem):
+    """Name of the kernel specialisation the problem maps to (host-only; raises IkgpuError when the
+    shape has no device kernel)."""
+    return _describe(capi.lib().ikgpu_problem_plan_constrained, problem)
+
+
+def tree_build(problem, visitor=None, p=None, pik_levels=0):
+    """Which compile-time build of the tree kernel a solve of the problem launches (host-only, include/ikgpu.h
+    ikgpu_dls_tree_build_plan): "<build>,<folded|unfolded>,<extras>,refill=<twin>", or "" when the solve does not run on the tree
+    kernel.  pik_levels: 0 for dls / dls_batch, 1 or 2 for pik with that many levels."""
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return _describe(capi.lib().ikgpu_dls_tree_build_plan, problem, C.byref(prm), pik_levels)
+
+
+def precompile(problem):
+    """Compile ahead of time (host-only, no device) what dls_data(problem) would compile at run time -- the structure-specialised
+    chain kernel of a chain without a pre-built instantiation -- into the on-disk cache; returns the kernel name.  Raises
+    IkgpuError (UNSUPPORTED) with the compiler's log when the compilation fails (the problem then runs on the general build)."""
+    return _describe(capi.lib().ikgpu_problem_precompile, problem)
+
+
+# ---- the device-tensor entry points (DESIGN.md section 3.6).  Each reads top to bottom: _prologue, the scalar checks, _batch, _check_slots
+# and _check_shape, _check_inputs, _outputs, data._bind, _launch.  A call with a wrong scalar, shape or container is refused before `data` is
+# looked at (tests/test_api_refusals_host.py).
+
+def _layout(layout):
+    return {"soa": capi.SOA, "aos": capi.AOS}[layout]   # (KeyError for an unknown name)
+
+
+def _prologue(problem, layout, visitor, p, params=_params):
+    """(model, ntasks, lay, prm) of a solve, with the defaults for the visitor and the parameters."""
+    lay = _layout(layout)
+    return problem.model(), problem.target_slots(), lay, params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+
+
+def _check_shape(name, t, shape):
+    """ValueError unless t (None: not given) has the shape; needs no device, and a wrong one would make the kernel read or write out
+    of bounds."""
+    if t is not None and tuple(getattr(t, "shape", ())) != tuple(shape):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(getattr(t, "shape", ())), tuple(shape)))
+
+
+def _check_dims(name, t, n):
+    if len(t.shape) != n:
+        raise ValueError("%s has shape %s, expected %d dimensions" % (name, tuple(t.shape), n))
+
+
+def _batch(lay, nq, name, Q0):
+    """(B, shape) of the configurations Q0: [nq, B] | [B, nq]."""
+    _check_dims(name, Q0, 2)
+    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
+    _check_shape(name, Q0, (nq, B) if lay == capi.SOA else (B, nq))
+    return B, tuple(Q0.shape)
+
+
+def _check_slots(lay, ntasks, B, name, X, lead=0):
+    """The targets-like X is `lead` leading axes (waypoints, vias, goals: outermost) in front of [ntasks, 12, B] | [B, ntasks, 12].
+    Returns the leading extents."""
+    _check_dims(name, X, 3 + lead)
+    extents = tuple(X.shape[:lead])
+    _check_shape(name, X, extents + ((ntasks, 12, B) if lay == capi.SOA else (B, ntasks, 12)))
+    return extents
+
+
+def _check_tensors(items, data):
+    """Device buffers handed to the C ABI as raw pointers, as (name, tensor, dtype): every one a CUDA tensor of its dtype (TypeError),
+    then every one on the problem's device and contiguous (ValueError).  With a wrong one the kernel would read or write out of
+    bounds, or through a pointer of another device."""
+    import torch
+    for name, t, dtype in items:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError("%s must be a CUDA tensor" % name)
+        if t.dtype != dtype:
+            raise TypeError("%s has dtype %s, expected %s" % (name, t.dtype, dtype))
+    for name, t, _ in items:
+        if t.device.index != data._device:
+            raise ValueError("%s lives on cuda:%s but the problem was created on device %d" % (name, t.device.index, data._device))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+
+
+def _check_inputs(data, **tensors):
+    """_check_tensors on the float64 inputs of a call, by argument name; an optional one that is None is skipped."""
+    import torch
+    _check_tensors([(name, t, torch.float64) for name, t in tensors.items() if t is not None], data)
+
+
+def _outputs(specs, like, data, out, label="out[{i}] ({name})", unused=0):
+    """The outputs of a call, specs = [(name, shape, dtype)]: allocated on like's device, or the caller's own tensors checked against
+    the specs.  The last `unused` entries of `out` are neither allocated nor checked (None when allocated, the caller's otherwise)."""
+    import torch
+    if out is None:
+        return [torch.empty(shape, dtype=dtype, device=like.device) for _, shape, dtype in specs] + [None] * unused
+    out = list(out)
+    if len(out) != len(specs) + unused:
+        raise ValueError("out holds %d entries, expected %d" % (len(out), len(specs) + unused))
+    for i, (t, (name, shape, dtype)) in enumerate(zip(out, specs)):   # (one output after the other, its shape last)
+        _check_tensors([(label.format(i=i, name=name), t, dtype)], data)
+        _check_shape(label.format(i=i, name=name), t, shape)
+    return out
+
+
+def _solve_outputs(qs, B, extra=()):
+    """The specs every solve shares -- Q like Q0, success and iterations per problem -- followed by `extra`."""
+    import torch
+    return [("Q", qs, torch.float64), ("success", (B,), torch.uint8), ("iterations", (B,), torch.int32)] + list(extra)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _seed(seed):
+    return seed & 0xFFFFFFFFFFFFFFFF
+
+
+def _launch(like, stream, fn, *args, workspace=None):
+    """capi.check(fn(*args[, workspace pointer, its size], stream)) on `stream`, or (None) on torch's current stream of like's device.
+    workspace = (size function, *its arguments): allocated for the call when the size is not 0 (0 for a single launch)."""
+    import torch
+    if workspace is not None:
+        nbytes = workspace[0](*workspace[1:])
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=like.device) if nbytes else None
+        args += (_ptr(ws), nbytes)
+    s = torch.cuda.current_stream(like.device).cuda_stream if stream is None else stream
+    capi.check(fn(*args, C.c_void_p(s)))
+
+
+def _kernel_name(fn, data, visitor, p, *extra):
+    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
+    return fn(data._h, C.byref(prm), *extra).decode()
 
 
 def dls(problem, q0, data, visitor=None, p=None):
@@ -538,50 +648,36 @@ def dls_batch(problem, Q0, targets, data, visitor=None, p=None, layout="soa", ou
       layout "soa": Q0 [nq, B], targets [ntasks, 12, B]   |   "aos": Q0 [B, nq], targets [B, ntasks, 12]
     Returns (Q, success uint8 [B], iterations int32 [B]) in the same container type as Q0.
     """
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    data._bind(problem)
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay ={"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
     L = capi.lib()
+    return _solve_batch(problem, Q0, targets, data, visitor, p, _params, layout, out, stream, L.ikgpu_dls_solve_batch_host, L.ikgpu_dls_solve_batch)
+
+
+def _solve_batch(problem, Q0, targets, data, visitor, p, params, layout, out, stream, host_fn, device_fn):
+    """dls_batch and pik_batch.  Unlike the later entries these bind first and test the container before the shapes: numpy arrays
+    are a container they take."""
+    data._bind(problem)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p, params)
     if isinstance(Q0, np.ndarray):
         Q0 = np.ascontiguousarray(Q0, dtype=np.float64)
         targets = np.ascontiguousarray(targets, dtype=np.float64)
-        B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-        _check_shapes(Q0.shape, targets.shape, model.nq, ntasks, B, lay)
+        B, _ = _batch(lay, model.nq, "Q0", Q0)
+        _check_slots(lay, ntasks, B, "targets", targets)
         Q = np.empty_like(Q0)
         ok = np.zeros(B, np.uint8)
         it = np.zeros(B, np.int32)
-        capi.check(L.ikgpu_dls_solve_batch_host(data._h, B, Q0.ctypes.data, targets.ctypes.data, C.byref(prm),
-                                                Q.ctypes.data, ok.ctypes.data, it.ctypes.data, lay))
+        capi.check(host_fn(data._h, B, Q0.ctypes.data, targets.ctypes.data, C.byref(prm), Q.ctypes.data, ok.ctypes.data, it.ctypes.data, lay))
         return Q, ok, it
-    import torch
-    if not (Q0.is_cuda and targets.is_cuda and Q0.dtype == torch.float64 and targets.dtype == torch.float64):
-        raise TypeError("dls_batch needs float64 CUDA tensors (or numpy arrays)")
-    if not (Q0.is_contiguous() and targets.is_contiguous()):
-        raise ValueError("dls_batch needs contiguous tensors")
-    if Q0.device.index != data._device:
-        raise ValueError("tensors live on cuda:%s but the problem was created on device %d" % (Q0.device.index, data._device))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
-    if out is None:
-        Q = torch.empty_like(Q0)
-        ok = torch.empty(B, dtype=torch.uint8, device=Q0.device)
-        it = torch.empty(B, dtype=torch.int32, device=Q0.device)
-    else:
-        Q, ok, it = _check_out(out, model.nq, B, lay, data._device)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_solve_batch(data._h, B, Q0.data_ptr(), targets.data_ptr(), C.byref(prm), Q.data_ptr(),
-                                       ok.data_ptr(), it.data_ptr(), lay, C.c_void_p(s)))
+    _check_inputs(data, Q0=Q0, targets=targets)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    _check_slots(lay, ntasks, B, "targets", targets)
+    Q, ok, it = _outputs(_solve_outputs(qs, B), Q0, data, out)
+    _launch(Q0, stream, device_fn, data._h, B, _ptr(Q0), _ptr(targets), C.byref(prm), _ptr(Q), _ptr(ok), _ptr(it), lay)
     return Q, ok, it
 
 
 def dls_track_kernel(data, visitor=None, p=None):
     """Name of what dls_track_batch runs for these parameters: "dls_chain_track<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_track_kernel(data._h, C.byref(prm)).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_track_kernel, data, visitor, p)
 
 
 def dls_track_batch(problem, Q0, targets, data, visitor=None, p=None, layout="soa", out=None, stream=None):
@@ -594,64 +690,35 @@ def dls_track_batch(problem, Q0, targets, data, visitor=None, p=None, layout="so
     out: (Q [T, nq, B] | [T, B, nq], success uint8 [T, B], iterations int32 [T, B]) preallocated, or None.
     Returns (Q, success, iterations)."""
     import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
-    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
-    if len(Q0.shape) != 2 or len(targets.shape) != 4:
-        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 4 dimensions (waypoints outermost)" % (tuple(Q0.shape), tuple(targets.shape)))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    T = targets.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(targets.shape[1:]), model.nq, ntasks, B, lay)
-    if not (isinstance(Q0, torch.Tensor) and isinstance(targets, torch.Tensor) and Q0.is_cuda and targets.is_cuda
-            and Q0.dtype == torch.float64 and targets.dtype == torch.float64):
-        raise TypeError("dls_track_batch needs float64 CUDA tensors")
-    if not (Q0.is_contiguous() and targets.is_contiguous()):
-        raise ValueError("dls_track_batch needs contiguous tensors")
-    if Q0.device.index != data._device or targets.device.index != data._device:
-        raise ValueError("tensors live on cuda:%s / cuda:%s but the problem was created on device %d"
-                         % (Q0.device.index, targets.device.index, data._device))
-    q_shape = (T, model.nq, B) if lay == capi.SOA else (T, B, model.nq)
-    if out is None:
-        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
-        ok = torch.empty((T, B), dtype=torch.uint8, device=Q0.device)
-        it = torch.empty((T, B), dtype=torch.int32, device=Q0.device)
-    else:
-        Q, ok, it = out
-        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
-        _check_tensor("out[1] (success)", ok, (T, B), torch.uint8, data._device)
-        _check_tensor("out[2] (iterations)", it, (T, B), torch.int32, data._device)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    T, = _check_slots(lay, ntasks, B, "targets", targets, lead=1)
+    _check_inputs(data, Q0=Q0, targets=targets)
+    Q, ok, it = _outputs([("Q", (T,) + qs, torch.float64), ("success", (T, B), torch.uint8), ("iterations", (T, B), torch.int32)], Q0, data, out)
     data._bind(problem)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(capi.lib().ikgpu_dls_track_batch(data._h, B, T, Q0.data_ptr(), targets.data_ptr(), C.byref(prm), Q.data_ptr(),
-                                                ok.data_ptr(), it.data_ptr(), lay, C.c_void_p(s)))
+    _launch(Q0, stream, capi.lib().ikgpu_dls_track_batch, data._h, B, T, _ptr(Q0), _ptr(targets), C.byref(prm), _ptr(Q), _ptr(ok), _ptr(it), lay)
     return Q, ok, it
-
-
-def _check_line_inputs(who, Q0, goals, model, ntasks, lay, data):
-    """Shape, dtype, device and contiguity of (Q0, goals) of the line entries, shapes first (they need no device).  Returns B."""
-    import torch
-    if len(Q0.shape) != 2 or len(goals.shape) != 3:
-        raise ValueError("Q0 has shape %s and goals %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(goals.shape)))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(goals.shape), model.nq, ntasks, B, lay)
-    if not (isinstance(Q0, torch.Tensor) and isinstance(goals, torch.Tensor) and Q0.is_cuda and goals.is_cuda
-            and Q0.dtype == torch.float64 and goals.dtype == torch.float64):
-        raise TypeError("%s needs float64 CUDA tensors" % who)
-    if not (Q0.is_contiguous() and goals.is_contiguous()):
-        raise ValueError("%s needs contiguous tensors" % who)
-    if Q0.device.index != data._device or goals.device.index != data._device:
-        raise ValueError("tensors live on cuda:%s / cuda:%s but the problem was created on device %d"
-                         % (Q0.device.index, goals.device.index, data._device))
-    return B
 
 
 def _check_waypoints(T):
     if not isinstance(T, int) or T < 0:
         raise ValueError("T must be a non-negative integer, got %r" % (T,))
+
+
+def _check_vias(P):
+    if P < 1:
+        raise ValueError("vias holds no via pose (P must be at least 1)")
+
+
+def _check_joint_step(max_joint_step):
+    if not isinstance(max_joint_step, (int, float)) or not math.isfinite(max_joint_step) or max_joint_step < 0:
+        raise ValueError("max_joint_step must be finite and not negative (0: no joint-step rule), got %r" % (max_joint_step,))
+
+
+def _trajectory_outputs(N, qs, B):
+    """The specs of a job that writes N slabs of Q / success / iterations and how many of them each problem reached."""
+    import torch
+    return [("Q", (N,) + qs, torch.float64), ("success", (N, B), torch.uint8), ("iterations", (N, B), torch.int32), ("reached", (B,), torch.int32)]
 
 
 def line_targets(problem, Q0, goals, data, T, layout="soa"):
@@ -662,22 +729,20 @@ def line_targets(problem, Q0, goals, data, T, layout="soa"):
     float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], goals [ntasks, 12, B]   |   "aos": Q0 [B, nq], goals [B, ntasks, 12].
     Returns W [T, ntasks, 12, B] | [T, B, ntasks, 12], the shape of dls_track_batch's targets."""
     import torch
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    model, ntasks, lay = problem.model(), problem.target_slots(), _layout(layout)
     _check_waypoints(T)
-    B = _check_line_inputs("line_targets", Q0, goals, model, ntasks, lay, data)
+    B, _ = _batch(lay, model.nq, "Q0", Q0)
+    _check_slots(lay, ntasks, B, "goals", goals)
+    _check_inputs(data, Q0=Q0, goals=goals)
     W = torch.empty((T,) + tuple(goals.shape), dtype=torch.float64, device=Q0.device)
     data._bind(problem)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream
-    capi.check(capi.lib().ikgpu_line_targets(data._h, B, T, Q0.data_ptr(), goals.data_ptr(), W.data_ptr(), lay, C.c_void_p(s)))
+    _launch(Q0, None, capi.lib().ikgpu_line_targets, data._h, B, T, _ptr(Q0), _ptr(goals), _ptr(W), lay)
     return W
 
 
 def dls_line_kernel(data, visitor=None, p=None):
     """Name of what dls_line_batch runs for these parameters: "dls_chain_line<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_line_kernel(data._h, C.byref(prm)).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_line_kernel, data, visitor, p)
 
 
 def dls_line_batch(problem, Q0, goals, data, T, visitor=None, p=None, layout="soa", out=None, stream=None):
@@ -691,55 +756,17 @@ def dls_line_batch(problem, Q0, goals, data, T, visitor=None, p=None, layout="so
     float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], goals [ntasks, 12, B]   |   "aos": Q0 [B, nq], goals [B, ntasks, 12].
     out: (Q [T, nq, B] | [T, B, nq], success uint8 [T, B], iterations int32 [T, B], reached int32 [B]) preallocated, or None.
     Returns (Q, success, iterations, reached)."""
-    import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
     _check_waypoints(T)
-    B = _check_line_inputs("dls_line_batch", Q0, goals, model, ntasks, lay, data)
-    q_shape = (T, model.nq, B) if lay == capi.SOA else (T, B, model.nq)
-    if out is None:
-        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
-        ok = torch.empty((T, B), dtype=torch.uint8, device=Q0.device)
-        it = torch.empty((T, B), dtype=torch.int32, device=Q0.device)
-        reached = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-    else:
-        Q, ok, it, reached = out
-        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
-        _check_tensor("out[1] (success)", ok, (T, B), torch.uint8, data._device)
-        _check_tensor("out[2] (iterations)", it, (T, B), torch.int32, data._device)
-        _check_tensor("out[3] (reached)", reached, (B,), torch.int32, data._device)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    _check_slots(lay, ntasks, B, "goals", goals)
+    _check_inputs(data, Q0=Q0, goals=goals)
+    Q, ok, it, reached = _outputs(_trajectory_outputs(T, qs, B), Q0, data, out)
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_line_workspace_bytes(data._h, B, T, C.byref(prm))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_line_batch(data._h, B, T, Q0.data_ptr(), goals.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
-                                      reached.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_line_batch, data._h, B, T, _ptr(Q0), _ptr(goals), C.byref(prm), _ptr(Q), _ptr(ok), _ptr(it), _ptr(reached), lay,
+            workspace=(L.ikgpu_dls_line_workspace_bytes, data._h, B, T, C.byref(prm)))
     return Q, ok, it, reached
-
-
-def _check_path_inputs(who, Q0, vias, model, ntasks, lay, data):
-    """_check_line_inputs for (Q0, vias): vias is P slabs of what the line entries take as goals.  Returns (B, P)."""
-    if len(Q0.shape) != 2 or len(vias.shape) != 4:
-        raise ValueError("Q0 has shape %s and vias %s, expected 2 and 4 dimensions (via poses outermost)" % (tuple(Q0.shape), tuple(vias.shape)))
-    if vias.shape[0] < 1:
-        raise ValueError("vias holds no via pose (P must be at least 1)")
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(vias.shape[1:]), model.nq, ntasks, B, lay)
-    import torch
-    if not (isinstance(Q0, torch.Tensor) and isinstance(vias, torch.Tensor) and Q0.is_cuda and vias.is_cuda
-            and Q0.dtype == torch.float64 and vias.dtype == torch.float64):
-        raise TypeError("%s needs float64 CUDA tensors" % who)
-    if not (Q0.is_contiguous() and vias.is_contiguous()):
-        raise ValueError("%s needs contiguous tensors" % who)
-    if Q0.device.index != data._device or vias.device.index != data._device:
-        raise ValueError("tensors live on cuda:%s / cuda:%s but the problem was created on device %d"
-                         % (Q0.device.index, vias.device.index, data._device))
-    return B, vias.shape[0]
 
 
 def path_targets(problem, Q0, vias, data, T, layout="soa"):
@@ -750,22 +777,21 @@ def path_targets(problem, Q0, vias, data, T, layout="soa"):
     float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], vias [P, ntasks, 12, B]   |   "aos": Q0 [B, nq], vias [P, B, ntasks, 12].
     Returns W [P T, ntasks, 12, B] | [P T, B, ntasks, 12], the shape of dls_track_batch's targets."""
     import torch
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
+    model, ntasks, lay = problem.model(), problem.target_slots(), _layout(layout)
     _check_waypoints(T)
-    B, P = _check_path_inputs("path_targets", Q0, vias, model, ntasks, lay, data)
+    B, _ = _batch(lay, model.nq, "Q0", Q0)
+    P, = _check_slots(lay, ntasks, B, "vias", vias, lead=1)
+    _check_vias(P)
+    _check_inputs(data, Q0=Q0, vias=vias)
     W = torch.empty((P * T,) + tuple(vias.shape[1:]), dtype=torch.float64, device=Q0.device)
     data._bind(problem)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream
-    capi.check(capi.lib().ikgpu_path_targets(data._h, B, P, T, Q0.data_ptr(), vias.data_ptr(), W.data_ptr(), lay, C.c_void_p(s)))
+    _launch(Q0, None, capi.lib().ikgpu_path_targets, data._h, B, P, T, _ptr(Q0), _ptr(vias), _ptr(W), lay)
     return W
 
 
 def dls_path_kernel(data, visitor=None, p=None):
     """Name of what dls_path_batch runs for these parameters: "dls_chain_path<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_path_kernel(data._h, C.byref(prm)).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_path_kernel, data, visitor, p)
 
 
 def dls_path_batch(problem, Q0, vias, data, T, max_joint_step=0.0, visitor=None, p=None, layout="soa", out=None, stream=None):
@@ -781,45 +807,24 @@ def dls_path_batch(problem, Q0, vias, data, T, max_joint_step=0.0, visitor=None,
     float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], vias [P, ntasks, 12, B]   |   "aos": Q0 [B, nq], vias [P, B, ntasks, 12].
     out: (Q [P T, nq, B] | [P T, B, nq], success uint8 [P T, B], iterations int32 [P T, B], reached int32 [B]) preallocated, or None.
     Returns (Q, success, iterations, reached)."""
-    import math
-    import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
     _check_waypoints(T)
-    if not isinstance(max_joint_step, (int, float)) or not math.isfinite(max_joint_step) or max_joint_step < 0:
-        raise ValueError("max_joint_step must be finite and not negative (0: no joint-step rule), got %r" % (max_joint_step,))
-    B, P = _check_path_inputs("dls_path_batch", Q0, vias, model, ntasks, lay, data)
-    N = P * T
-    q_shape = (N, model.nq, B) if lay == capi.SOA else (N, B, model.nq)
-    if out is None:
-        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
-        ok = torch.empty((N, B), dtype=torch.uint8, device=Q0.device)
-        it = torch.empty((N, B), dtype=torch.int32, device=Q0.device)
-        reached = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-    else:
-        Q, ok, it, reached = out
-        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
-        _check_tensor("out[1] (success)", ok, (N, B), torch.uint8, data._device)
-        _check_tensor("out[2] (iterations)", it, (N, B), torch.int32, data._device)
-        _check_tensor("out[3] (reached)", reached, (B,), torch.int32, data._device)
+    _check_joint_step(max_joint_step)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    P, = _check_slots(lay, ntasks, B, "vias", vias, lead=1)
+    _check_vias(P)
+    _check_inputs(data, Q0=Q0, vias=vias)
+    Q, ok, it, reached = _outputs(_trajectory_outputs(P * T, qs, B), Q0, data, out)
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_path_workspace_bytes(data._h, B, P, T, C.byref(prm))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_path_batch(data._h, B, P, T, Q0.data_ptr(), vias.data_ptr(), C.byref(prm), float(max_joint_step), Q.data_ptr(), ok.data_ptr(),
-                                      it.data_ptr(), reached.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_path_batch, data._h, B, P, T, _ptr(Q0), _ptr(vias), C.byref(prm), float(max_joint_step), _ptr(Q), _ptr(ok), _ptr(it),
+            _ptr(reached), lay, workspace=(L.ikgpu_dls_path_workspace_bytes, data._h, B, P, T, C.byref(prm)))
     return Q, ok, it, reached
 
 
 def dls_multistart_kernel(data, visitor=None, p=None, num_starts=8):
     """Name of what dls_multistart_batch runs for these parameters: "dls_chain_multistart<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_multistart_kernel(data._h, C.byref(prm), num_starts).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_multistart_kernel, data, visitor, p, num_starts)
 
 
 def _check_starts(num_starts):
@@ -834,22 +839,12 @@ def multistart_starts(data, Q0, num_starts, seed=0, layout="soa"):
     only (include/ikgpu.h ikgpu_multistart_starts)."""
     import torch
     _check_starts(num_starts)
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    if len(Q0.shape) != 2:
-        raise ValueError("Q0 has shape %s, expected 2 dimensions" % (tuple(Q0.shape),))
-    if not (isinstance(Q0, torch.Tensor) and Q0.is_cuda and Q0.dtype == torch.float64):
-        raise TypeError("multistart_starts needs a float64 CUDA tensor")
-    if not Q0.is_contiguous():
-        raise ValueError("multistart_starts needs a contiguous tensor")
-    if Q0.device.index != data._device:
-        raise ValueError("Q0 lives on cuda:%s but the problem was created on device %d" % (Q0.device.index, data._device))
-    nq = len(data.support)
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    if tuple(Q0.shape) != ((nq, B) if lay == capi.SOA else (B, nq)):
-        raise ValueError("Q0 has shape %s, the problem has nq = %d" % (tuple(Q0.shape), nq))
-    out = torch.empty((num_starts - 1,) + tuple(Q0.shape), dtype=torch.float64, device=Q0.device)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream
-    capi.check(capi.lib().ikgpu_multistart_starts(data._h, B, num_starts, Q0.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), lay, C.c_void_p(s)))
+    lay = _layout(layout)
+    _check_dims("Q0", Q0, 2)
+    _check_inputs(data, Q0=Q0)   # (before the shape: nq is read from data)
+    B, qs = _batch(lay, len(data.support), "Q0", Q0)
+    out = torch.empty((num_starts - 1,) + qs, dtype=torch.float64, device=Q0.device)
+    _launch(Q0, None, capi.lib().ikgpu_multistart_starts, data._h, B, num_starts, _ptr(Q0), _seed(seed), _ptr(out), lay)
     return out
 
 
@@ -864,48 +859,17 @@ def dls_multistart_batch(problem, Q0, targets, data, visitor=None, p=None, num_s
     out: (Q, success uint8 [B], iterations int32 [B], winner int32 [B], err_sq float64 [B]) preallocated, or None.
     Returns (Q, success, iterations, winner, err_sq)."""
     import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
     _check_starts(num_starts)
-    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
-    if len(Q0.shape) != 2 or len(targets.shape) != 3:
-        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(targets.shape)))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
-    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
-        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
-    tensors = [Q0, targets] + ([starts] if starts is not None else [])
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
-        raise TypeError("dls_multistart_batch needs float64 CUDA tensors")
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError("dls_multistart_batch needs contiguous tensors")
-    if any(t.device.index != data._device for t in tensors):
-        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
-    if out is None:
-        Q = torch.empty_like(Q0)
-        ok = torch.empty((B,), dtype=torch.uint8, device=Q0.device)
-        it = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        win = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        err = torch.empty((B,), dtype=torch.float64, device=Q0.device)
-    else:
-        Q, ok, it, win, err = out
-        _check_tensor("out[0] (Q)", Q, tuple(Q0.shape), torch.float64, data._device)
-        _check_tensor("out[1] (success)", ok, (B,), torch.uint8, data._device)
-        _check_tensor("out[2] (iterations)", it, (B,), torch.int32, data._device)
-        _check_tensor("out[3] (winner)", win, (B,), torch.int32, data._device)
-        _check_tensor("out[4] (err_sq)", err, (B,), torch.float64, data._device)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    _check_slots(lay, ntasks, B, "targets", targets)
+    _check_shape("starts", starts, (num_starts - 1,) + qs)
+    _check_inputs(data, Q0=Q0, targets=targets, starts=starts)
+    Q, ok, it, win, err = _outputs(_solve_outputs(qs, B, [("winner", (B,), torch.int32), ("err_sq", (B,), torch.float64)]), Q0, data, out)
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_multistart_workspace_bytes(data._h, B, num_starts, C.byref(prm))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_multistart_batch(data._h, B, num_starts, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
-                                            seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
-                                            win.data_ptr(), err.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_multistart_batch, data._h, B, num_starts, _ptr(Q0), _ptr(starts), _seed(seed), _ptr(targets), C.byref(prm), _ptr(Q),
+            _ptr(ok), _ptr(it), _ptr(win), _ptr(err), lay, workspace=(L.ikgpu_dls_multistart_workspace_bytes, data._h, B, num_starts, C.byref(prm)))
     return Q, ok, it, win, err
 
 
@@ -916,8 +880,7 @@ PathMultistartResult = collections.namedtuple(
 def dls_path_multistart_kernel(data, visitor=None, p=None, num_starts=8):
     """Name of what dls_path_multistart_batch runs for these parameters: "dls_chain_path_multistart<...>" (the scout launch, followed by
     "dls_chain_path<...>" for the trajectory) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_path_multistart_kernel(data._h, C.byref(prm), num_starts).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_path_multistart_kernel, data, visitor, p, num_starts)
 
 
 def dls_path_multistart_batch(problem, Q0, vias, data, T, max_joint_step=0.0, visitor=None, p=None, num_starts=8, seed=0, starts=None,
@@ -935,60 +898,28 @@ def dls_path_multistart_batch(problem, Q0, vias, data, T, max_joint_step=0.0, vi
     out: a PathMultistartResult of preallocated tensors (q / success / iterations None with trajectory=False), or None.
     Returns PathMultistartResult(q_entry, entry_success, entry_iterations, winner, err_sq, reached int32 [B], reached_all int32 [K, B],
     q [(P-1) T, nq, B] | [(P-1) T, B, nq], success uint8 [(P-1) T, B], iterations int32 [(P-1) T, B])."""
-    import math
     import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
     _check_starts(num_starts)
     _check_waypoints(T)
-    if not isinstance(max_joint_step, (int, float)) or not math.isfinite(max_joint_step) or max_joint_step < 0:
-        raise ValueError("max_joint_step must be finite and not negative (0: no joint-step rule), got %r" % (max_joint_step,))
-    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
-    if starts is not None and tuple(getattr(starts, "shape", ())) != (num_starts - 1,) + tuple(Q0.shape):
-        raise ValueError("starts has shape %s, expected %s" % (tuple(getattr(starts, "shape", ())), (num_starts - 1,) + tuple(Q0.shape)))
-    B, P = _check_path_inputs("dls_path_multistart_batch", Q0, vias, model, ntasks, lay, data)
-    if starts is not None:
-        _check_tensor("starts", starts, (num_starts - 1,) + tuple(Q0.shape), torch.float64, data._device)
-    N = (P - 1) * T
-    K = num_starts
-    q_shape = (N, model.nq, B) if lay == capi.SOA else (N, B, model.nq)
-    dev = Q0.device
-    if out is None:
-        r = PathMultistartResult(
-            torch.empty_like(Q0), torch.empty((B,), dtype=torch.uint8, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
-            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
-            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((K, B), dtype=torch.int32, device=dev),
-            torch.empty(q_shape, dtype=torch.float64, device=dev) if trajectory else None,
-            torch.empty((N, B), dtype=torch.uint8, device=dev) if trajectory else None,
-            torch.empty((N, B), dtype=torch.int32, device=dev) if trajectory else None)
-    else:
-        r = PathMultistartResult(*out)
-        _check_tensor("out.q_entry", r.q_entry, tuple(Q0.shape), torch.float64, data._device)
-        _check_tensor("out.entry_success", r.entry_success, (B,), torch.uint8, data._device)
-        _check_tensor("out.entry_iterations", r.entry_iterations, (B,), torch.int32, data._device)
-        _check_tensor("out.winner", r.winner, (B,), torch.int32, data._device)
-        _check_tensor("out.err_sq", r.err_sq, (B,), torch.float64, data._device)
-        _check_tensor("out.reached", r.reached, (B,), torch.int32, data._device)
-        _check_tensor("out.reached_all", r.reached_all, (K, B), torch.int32, data._device)
-        if trajectory:
-            _check_tensor("out.q", r.q, q_shape, torch.float64, data._device)
-            _check_tensor("out.success", r.success, (N, B), torch.uint8, data._device)
-            _check_tensor("out.iterations", r.iterations, (N, B), torch.int32, data._device)
+    _check_joint_step(max_joint_step)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    P, = _check_slots(lay, ntasks, B, "vias", vias, lead=1)
+    _check_vias(P)
+    _check_shape("starts", starts, (num_starts - 1,) + qs)
+    _check_inputs(data, Q0=Q0, vias=vias, starts=starts)
+    N, K = (P - 1) * T, num_starts
+    f64, u8, i32 = torch.float64, torch.uint8, torch.int32
+    specs = list(zip(PathMultistartResult._fields, (qs, (B,), (B,), (B,), (B,), (B,), (K, B), (N,) + qs, (N, B), (N, B)),
+                     (f64, u8, i32, i32, f64, i32, i32, f64, u8, i32)))
+    kept = 10 if trajectory else 7    # trajectory=False: q / success / iterations are neither allocated nor checked
+    r = PathMultistartResult(*_outputs(specs[:kept], Q0, data, out, "out.{name}", unused=10 - kept))
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_path_multistart_workspace_bytes(data._h, B, K, P, T, C.byref(prm), 1 if trajectory else 0)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None   # (0 for the two launches: nothing allocated)
-    s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_path_multistart_batch(
-        data._h, B, K, P, T, Q0.data_ptr(), starts.data_ptr() if starts is not None else None, seed & 0xFFFFFFFFFFFFFFFF, vias.data_ptr(),
-        C.byref(prm), float(max_joint_step), r.q_entry.data_ptr(), r.entry_success.data_ptr(), r.entry_iterations.data_ptr(), r.winner.data_ptr(),
-        r.err_sq.data_ptr(), r.reached.data_ptr(), r.reached_all.data_ptr(), r.q.data_ptr() if trajectory else None,
-        r.success.data_ptr() if trajectory else None, r.iterations.data_ptr() if trajectory else None, lay,
-        ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_path_multistart_batch, data._h, B, K, P, T, _ptr(Q0), _ptr(starts), _seed(seed), _ptr(vias), C.byref(prm),
+            float(max_joint_step), _ptr(r.q_entry), _ptr(r.entry_success), _ptr(r.entry_iterations), _ptr(r.winner), _ptr(r.err_sq), _ptr(r.reached),
+            _ptr(r.reached_all), *(_ptr(t) if trajectory else None for t in (r.q, r.success, r.iterations)), lay,
+            workspace=(L.ikgpu_dls_path_multistart_workspace_bytes, data._h, B, K, P, T, C.byref(prm), 1 if trajectory else 0))
     return r
 
 
@@ -1002,8 +933,7 @@ class PickRule(enum.IntEnum):
 
 def dls_pick_kernel(data, visitor=None, p=None, num_starts=8, rule=PickRule.DISTANCE):
     """Name of what dls_pick_batch runs for these parameters: "dls_chain_pick<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_pick_kernel(data._h, C.byref(prm), num_starts, int(PickRule(rule))).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_pick_kernel, data, visitor, p, num_starts, int(PickRule(rule)))
 
 
 def dls_pick_batch(problem, Q0, targets, data, visitor=None, p=None, num_starts=8, rule=PickRule.DISTANCE, q_ref=None, weights=None, seed=0,
@@ -1019,67 +949,33 @@ def dls_pick_batch(problem, Q0, targets, data, visitor=None, p=None, num_starts=
     out: (Q, success uint8 [B], iterations int32 [B], winner int32 [B], cost float64 [B], err_sq float64 [B]) preallocated, or None.
     Returns (Q, success, iterations, winner, cost, err_sq)."""
     import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
     _check_starts(num_starts)
     rule = int(PickRule(rule))
-    if len(Q0.shape) != 2 or len(targets.shape) != 3:
-        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(targets.shape)))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
-    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
-        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
-    if q_ref is not None and tuple(q_ref.shape) != tuple(Q0.shape):
-        raise ValueError("q_ref has shape %s, expected %s" % (tuple(q_ref.shape), tuple(Q0.shape)))
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    _check_slots(lay, ntasks, B, "targets", targets)
+    _check_shape("starts", starts, (num_starts - 1,) + qs)
+    _check_shape("q_ref", q_ref, qs)
     w = None
     if weights is not None:
         w = [float(x) for x in weights]
         if len(w) != model.nq:
             raise ValueError("weights has %d entries, the model has nq = %d" % (len(w), model.nq))
         w = (C.c_double * model.nq)(*w)
-    tensors = [Q0, targets] + ([starts] if starts is not None else []) + ([q_ref] if q_ref is not None else [])
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
-        raise TypeError("dls_pick_batch needs float64 CUDA tensors")
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError("dls_pick_batch needs contiguous tensors")
-    if any(t.device.index != data._device for t in tensors):
-        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
-    if out is None:
-        Q = torch.empty_like(Q0)
-        ok = torch.empty((B,), dtype=torch.uint8, device=Q0.device)
-        it = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        win = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        cost = torch.empty((B,), dtype=torch.float64, device=Q0.device)
-        err = torch.empty((B,), dtype=torch.float64, device=Q0.device)
-    else:
-        Q, ok, it, win, cost, err = out
-        _check_tensor("out[0] (Q)", Q, tuple(Q0.shape), torch.float64, data._device)
-        _check_tensor("out[1] (success)", ok, (B,), torch.uint8, data._device)
-        _check_tensor("out[2] (iterations)", it, (B,), torch.int32, data._device)
-        _check_tensor("out[3] (winner)", win, (B,), torch.int32, data._device)
-        _check_tensor("out[4] (cost)", cost, (B,), torch.float64, data._device)
-        _check_tensor("out[5] (err_sq)", err, (B,), torch.float64, data._device)
+    _check_inputs(data, Q0=Q0, targets=targets, starts=starts, q_ref=q_ref)
+    Q, ok, it, win, cost, err = _outputs(_solve_outputs(qs, B, [("winner", (B,), torch.int32), ("cost", (B,), torch.float64),
+                                                               ("err_sq", (B,), torch.float64)]), Q0, data, out)
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_pick_workspace_bytes(data._h, B, num_starts, C.byref(prm))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_pick_batch(data._h, B, num_starts, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
-                                      seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), rule,
-                                      q_ref.data_ptr() if q_ref is not None else None, w, Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
-                                      win.data_ptr(), cost.data_ptr(), err.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes,
-                                      C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_pick_batch, data._h, B, num_starts, _ptr(Q0), _ptr(starts), _seed(seed), _ptr(targets), C.byref(prm), rule,
+            _ptr(q_ref), w, _ptr(Q), _ptr(ok), _ptr(it), _ptr(win), _ptr(cost), _ptr(err), lay,
+            workspace=(L.ikgpu_dls_pick_workspace_bytes, data._h, B, num_starts, C.byref(prm)))
     return Q, ok, it, win, cost, err
 
 
 def dls_solutions_kernel(data, visitor=None, p=None, num_starts=8):
     """Name of what dls_solutions_batch runs for these parameters: "dls_chain_solutions<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_solutions_kernel(data._h, C.byref(prm), num_starts).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_solutions_kernel, data, visitor, p, num_starts)
 
 
 def dls_solutions_batch(problem, Q0, targets, data, visitor=None, p=None, num_starts=8, max_solutions=None, separation=0.1, seed=0, starts=None,
@@ -1094,14 +990,8 @@ def dls_solutions_batch(problem, Q0, targets, data, visitor=None, p=None, num_st
     float64 CUDA tensors, contiguous: layout "soa": Q0 [nq, B], targets [ntasks, 12, B]   |   "aos": Q0 [B, nq], targets [B, ntasks, 12]
     out: (Q [N, nq, B] | [N, B, nq], count int32 [B], which int32 [N, B], iterations int32 [N, B]) preallocated, or None.
     Returns (Q, count, which, iterations); slots n >= count[b] of problem b are not written."""
-    import math
     import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
     _check_starts(num_starts)
     N = num_starts if max_solutions is None else max_solutions
     if not isinstance(N, int) or not 1 <= N <= num_starts:
@@ -1109,40 +999,16 @@ def dls_solutions_batch(problem, Q0, targets, data, visitor=None, p=None, num_st
     separation = float(separation)
     if not (math.isfinite(separation) and separation >= 0.0):
         raise ValueError("separation must be finite and not negative, got %r" % (separation,))
-    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
-    if len(Q0.shape) != 2 or len(targets.shape) != 3:
-        raise ValueError("Q0 has shape %s and targets %s, expected 2 and 3 dimensions" % (tuple(Q0.shape), tuple(targets.shape)))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
-    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
-        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
-    tensors = [Q0, targets] + ([starts] if starts is not None else [])
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
-        raise TypeError("dls_solutions_batch needs float64 CUDA tensors")
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError("dls_solutions_batch needs contiguous tensors")
-    if any(t.device.index != data._device for t in tensors):
-        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
-    q_shape = (N,) + tuple(Q0.shape)
-    if out is None:
-        Q = torch.empty(q_shape, dtype=torch.float64, device=Q0.device)
-        count = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        which = torch.empty((N, B), dtype=torch.int32, device=Q0.device)
-        it = torch.empty((N, B), dtype=torch.int32, device=Q0.device)
-    else:
-        Q, count, which, it = out
-        _check_tensor("out[0] (Q)", Q, q_shape, torch.float64, data._device)
-        _check_tensor("out[1] (count)", count, (B,), torch.int32, data._device)
-        _check_tensor("out[2] (which)", which, (N, B), torch.int32, data._device)
-        _check_tensor("out[3] (iterations)", it, (N, B), torch.int32, data._device)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    _check_slots(lay, ntasks, B, "targets", targets)
+    _check_shape("starts", starts, (num_starts - 1,) + qs)
+    _check_inputs(data, Q0=Q0, targets=targets, starts=starts)
+    Q, count, which, it = _outputs([("Q", (N,) + qs, torch.float64), ("count", (B,), torch.int32), ("which", (N, B), torch.int32),
+                                    ("iterations", (N, B), torch.int32)], Q0, data, out)
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_solutions_workspace_bytes(data._h, B, num_starts, N, C.byref(prm))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_solutions_batch(data._h, B, num_starts, N, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
-                                           seed & 0xFFFFFFFFFFFFFFFF, targets.data_ptr(), C.byref(prm), separation, Q.data_ptr(), count.data_ptr(),
-                                           which.data_ptr(), it.data_ptr(), lay, ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_solutions_batch, data._h, B, num_starts, N, _ptr(Q0), _ptr(starts), _seed(seed), _ptr(targets), C.byref(prm), separation,
+            _ptr(Q), _ptr(count), _ptr(which), _ptr(it), lay, workspace=(L.ikgpu_dls_solutions_workspace_bytes, data._h, B, num_starts, N, C.byref(prm)))
     return Q, count, which, it
 
 
@@ -1154,8 +1020,7 @@ def _check_goalset_size(num_goals, num_starts):
 
 def dls_goalset_kernel(data, visitor=None, p=None, num_goals=4, num_starts=1):
     """Name of what dls_goalset_batch runs for these parameters: "dls_chain_goalset<...>" (one launch) or "loop(<data.kernel>)"."""
-    prm = _params(visitor or inverse_kinematics_visitor(), p or dls_parameters())
-    return capi.lib().ikgpu_dls_goalset_kernel(data._h, C.byref(prm), num_goals, num_starts).decode()
+    return _kernel_name(capi.lib().ikgpu_dls_goalset_kernel, data, visitor, p, num_goals, num_starts)
 
 
 def dls_goalset_batch(problem, Q0, goals, data, visitor=None, p=None, num_starts=1, seed=0, starts=None, layout="soa", out=None, stream=None):
@@ -1170,89 +1035,20 @@ def dls_goalset_batch(problem, Q0, goals, data, visitor=None, p=None, num_starts
     out: (Q, success uint8 [B], iterations int32 [B], goal int32 [B], start int32 [B], err_sq float64 [B], reachable uint8 [G, B])
     preallocated, or None.  Returns (Q, success, iterations, goal, start, err_sq, reachable)."""
     import torch
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or dls_parameters()
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = _params(visitor, p)
-    # shapes first (they need no device): a wrong one would make the kernel read or write out of bounds
-    if len(Q0.shape) != 2 or len(goals.shape) != 4:
-        raise ValueError("Q0 has shape %s and goals %s, expected 2 and 4 dimensions" % (tuple(Q0.shape), tuple(goals.shape)))
-    G = int(goals.shape[0])
+    model, ntasks, lay, prm = _prologue(problem, layout, visitor, p)
+    B, qs = _batch(lay, model.nq, "Q0", Q0)
+    G, = _check_slots(lay, ntasks, B, "goals", goals, lead=1)
     _check_goalset_size(G, num_starts)
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(goals.shape[1:]), model.nq, ntasks, B, lay)
-    if starts is not None and tuple(starts.shape) != (num_starts - 1,) + tuple(Q0.shape):
-        raise ValueError("starts has shape %s, expected %s" % (tuple(starts.shape), (num_starts - 1,) + tuple(Q0.shape)))
-    tensors = [Q0, goals] + ([starts] if starts is not None else [])
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in tensors):
-        raise TypeError("dls_goalset_batch needs float64 CUDA tensors")
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError("dls_goalset_batch needs contiguous tensors")
-    if any(t.device.index != data._device for t in tensors):
-        raise ValueError("tensors live on %s but the problem was created on device %d" % ([str(t.device) for t in tensors], data._device))
-    if out is None:
-        Q = torch.empty_like(Q0)
-        ok = torch.empty((B,), dtype=torch.uint8, device=Q0.device)
-        it = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        goal = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        start = torch.empty((B,), dtype=torch.int32, device=Q0.device)
-        err = torch.empty((B,), dtype=torch.float64, device=Q0.device)
-        reach = torch.empty((G, B), dtype=torch.uint8, device=Q0.device)
-    else:
-        Q, ok, it, goal, start, err, reach = out
-        _check_tensor("out[0] (Q)", Q, tuple(Q0.shape), torch.float64, data._device)
-        _check_tensor("out[1] (success)", ok, (B,), torch.uint8, data._device)
-        _check_tensor("out[2] (iterations)", it, (B,), torch.int32, data._device)
-        _check_tensor("out[3] (goal)", goal, (B,), torch.int32, data._device)
-        _check_tensor("out[4] (start)", start, (B,), torch.int32, data._device)
-        _check_tensor("out[5] (err_sq)", err, (B,), torch.float64, data._device)
-        _check_tensor("out[6] (reachable)", reach, (G, B), torch.uint8, data._device)
+    _check_shape("starts", starts, (num_starts - 1,) + qs)
+    _check_inputs(data, Q0=Q0, goals=goals, starts=starts)
+    Q, ok, it, goal, start, err, reach = _outputs(_solve_outputs(qs, B, [("goal", (B,), torch.int32), ("start", (B,), torch.int32),
+                                                                        ("err_sq", (B,), torch.float64), ("reachable", (G, B), torch.uint8)]), Q0, data, out)
     data._bind(problem)
     L = capi.lib()
-    nbytes = L.ikgpu_dls_goalset_workspace_bytes(data._h, B, G, num_starts, C.byref(prm))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q0.device) if nbytes else None   # (0 for the single launch: nothing allocated)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_dls_goalset_batch(data._h, B, G, num_starts, Q0.data_ptr(), starts.data_ptr() if starts is not None else None,
-                                         seed & 0xFFFFFFFFFFFFFFFF, goals.data_ptr(), C.byref(prm), Q.data_ptr(), ok.data_ptr(), it.data_ptr(),
-                                         goal.data_ptr(), start.data_ptr(), err.data_ptr(), reach.data_ptr(), lay,
-                                         ws.data_ptr() if ws is not None else None, nbytes, C.c_void_p(s)))
+    _launch(Q0, stream, L.ikgpu_dls_goalset_batch, data._h, B, G, num_starts, _ptr(Q0), _ptr(starts), _seed(seed), _ptr(goals), C.byref(prm), _ptr(Q), _ptr(ok),
+            _ptr(it), _ptr(goal), _ptr(start), _ptr(err), _ptr(reach), lay,
+            workspace=(L.ikgpu_dls_goalset_workspace_bytes, data._h, B, G, num_starts, C.byref(prm)))
     return Q, ok, it, goal, start, err, reach
-
-
-def _check_tensor(name, t, shape, dtype, device):
-    """A device buffer handed to the C ABI as a raw pointer: wrong dtype / device / stride / size would make the kernel read or
-    write out of bounds, so it is refused here."""
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError("%s must be a CUDA tensor" % name)
-    if t.dtype != dtype:
-        raise TypeError("%s has dtype %s, expected %s" % (name, t.dtype, dtype))
-    if t.device.index != device:
-        raise ValueError("%s lives on cuda:%s but the problem was created on device %d" % (name, t.device.index, device))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-
-
-def _check_out(out, nq, B, lay, device):
-    import torch
-    Q, ok, it = out
-    _check_tensor("out[0] (Q)", Q, (nq, B) if lay == capi.SOA else (B, nq), torch.float64, device)
-    _check_tensor("out[1] (success)", ok, (B,), torch.uint8, device)
-    _check_tensor("out[2] (iterations)", it, (B,), torch.int32, device)
-    return Q, ok, it
-
-
-def _check_shapes(qs, ts, nq, ntasks, B, lay):
-    want_q = (nq, B) if lay == capi.SOA else (B, nq)
-    want_t = (ntasks, 12, B) if lay == capi.SOA else (B, ntasks, 12)
-    if tuple(qs) != want_q:
-        raise ValueError("Q0 has shape %s, expected %s" % (tuple(qs), want_q))
-    if tuple(ts) != want_t:
-        raise ValueError("targets has shape %s, expected %s" % (tuple(ts), want_t))
 
 
 class pik_parameters:
@@ -1335,44 +1131,9 @@ def pik(problem, q0, data, visitor=None, p=None):
 
 def pik_batch(problem, Q0, targets, data, visitor=None, p=None, layout="soa", out=None, stream=None):
     """B independent ik::pik() calls in lockstep on the device; arguments and return value as dls_batch."""
-    visitor = visitor or inverse_kinematics_visitor()
-    p = p or pik_parameters()
-    data._bind(problem)
-    model = problem.model()
-    ntasks = problem.target_slots()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    prm = data._params(visitor, p)
     L = capi.lib()
-    if isinstance(Q0, np.ndarray):
-        Q0 = np.ascontiguousarray(Q0, dtype=np.float64)
-        targets = np.ascontiguousarray(targets, dtype=np.float64)
-        B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-        _check_shapes(Q0.shape, targets.shape, model.nq, ntasks, B, lay)
-        Q = np.empty_like(Q0)
-        ok = np.zeros(B, np.uint8)
-        it = np.zeros(B, np.int32)
-        capi.check(L.ikgpu_pik_solve_batch_host(data._h, B, Q0.ctypes.data, targets.ctypes.data, C.byref(prm),
-                                                Q.ctypes.data, ok.ctypes.data, it.ctypes.data, lay))
-        return Q, ok, it
-    import torch
-    if not (Q0.is_cuda and targets.is_cuda and Q0.dtype == torch.float64 and targets.dtype == torch.float64):
-        raise TypeError("pik_batch needs float64 CUDA tensors (or numpy arrays)")
-    if not (Q0.is_contiguous() and targets.is_contiguous()):
-        raise ValueError("pik_batch needs contiguous tensors")
-    if Q0.device.index != data._device:
-        raise ValueError("tensors live on cuda:%s but the problem was created on device %d" % (Q0.device.index, data._device))
-    B = Q0.shape[1] if lay == capi.SOA else Q0.shape[0]
-    _check_shapes(tuple(Q0.shape), tuple(targets.shape), model.nq, ntasks, B, lay)
-    if out is None:
-        Q = torch.empty_like(Q0)
-        ok = torch.empty(B, dtype=torch.uint8, device=Q0.device)
-        it = torch.empty(B, dtype=torch.int32, device=Q0.device)
-    else:
-        Q, ok, it = _check_out(out, model.nq, B, lay, data._device)
-    s = torch.cuda.current_stream(Q0.device).cuda_stream if stream is None else stream
-    capi.check(L.ikgpu_pik_solve_batch(data._h, B, Q0.data_ptr(), targets.data_ptr(), C.byref(prm), Q.data_ptr(),
-                                       ok.data_ptr(), it.data_ptr(), lay, C.c_void_p(s)))
-    return Q, ok, it
+    return _solve_batch(problem, Q0, targets, data, visitor, p or pik_parameters(), data._params, layout, out, stream, L.ikgpu_pik_solve_batch_host,
+                        L.ikgpu_pik_solve_batch)
 
 
 def evaluate_batch(problem, Q, targets, data, layout="soa", jacobian=True):
@@ -1380,20 +1141,15 @@ def evaluate_batch(problem, Q, targets, data, layout="soa", jacobian=True):
     batch, on the device: returns (e [M, B], J [M, nv, B]) for "soa" ([B, M], [B, M, nv] for "aos")."""
     import torch
     data._bind(problem)
-    model = problem.model()
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    B = Q.shape[1] if lay == capi.SOA else Q.shape[0]
+    model, nt, lay = problem.model(), problem.target_slots(), _layout(layout)
+    _check_inputs(data, Q=Q)   # (one argument after the other, its shape last)
+    B, _ = _batch(lay, model.nq, "Q", Q)
+    _check_inputs(data, targets=targets)
+    _check_slots(lay, nt, B, "targets", targets)
     M = data.rows
-    nt = problem.target_slots()
-    _check_tensor("Q", Q, (model.nq, B) if lay == capi.SOA else (B, model.nq), torch.float64, data._device)
-    _check_tensor("targets", targets, (nt, 12, B) if lay == capi.SOA else (B, nt, 12), torch.float64, data._device)
     e = torch.empty((M, B) if lay == capi.SOA else (B, M), dtype=torch.float64, device=Q.device)
-    J = None
-    if jacobian:
-        J = torch.empty((M, model.nv, B) if lay == capi.SOA else (B, M, model.nv), dtype=torch.float64, device=Q.device)
-    s = torch.cuda.current_stream(Q.device).cuda_stream
-    capi.check(capi.lib().ikgpu_evaluate_batch(data._h, B, Q.data_ptr(), targets.data_ptr(), e.data_ptr(),
-                                               J.data_ptr() if jacobian else None, lay, C.c_void_p(s)))
+    J = torch.empty((M, model.nv, B) if lay == capi.SOA else (B, M, model.nv), dtype=torch.float64, device=Q.device) if jacobian else None
+    _launch(Q, None, capi.lib().ikgpu_evaluate_batch, data._h, B, _ptr(Q), _ptr(targets), _ptr(e), _ptr(J), lay)
     return e, J
 
 
@@ -1402,12 +1158,9 @@ def task_frames_fk_batch(problem, Q, data, layout="soa"):
     ik/ik/data.cpp:28-29): [ntasks, 12, B] ("soa") or [B, ntasks, 12] ("aos")."""
     import torch
     data._bind(problem)
-    lay = {"soa": capi.SOA, "aos": capi.AOS}[layout]
-    B = Q.shape[1] if lay == capi.SOA else Q.shape[0]
-    nt = problem.target_slots()
-    nq = problem.model().nq
-    _check_tensor("Q", Q, (nq, B) if lay == capi.SOA else (B, nq), torch.float64, data._device)
+    model, nt, lay = problem.model(), problem.target_slots(), _layout(layout)
+    _check_inputs(data, Q=Q)
+    B, _ = _batch(lay, model.nq, "Q", Q)
     out = torch.empty((nt, 12, B) if lay == capi.SOA else (B, nt, 12), dtype=torch.float64, device=Q.device)
-    s = torch.cuda.current_stream(Q.device).cuda_stream
-    capi.check(capi.lib().ikgpu_task_frames_fk_batch(data._h, B, Q.data_ptr(), out.data_ptr(), lay, C.c_void_p(s)))
+    _launch(Q, None, capi.lib().ikgpu_task_frames_fk_batch, data._h, B, _ptr(Q), _ptr(out), lay)
     return out
