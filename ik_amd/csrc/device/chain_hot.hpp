@@ -537,18 +537,30 @@ IKD_FN void hot_dls(const Tab &t, const LoopParams &prm, double (&q)[NJ], const 
 }
 
 // Entries of q outside the task support: dq = 0 there, so the loop only ever clips them to the limits (reference
-// ik/ik/dls.cpp:71 clips the whole q after each step; no step is taken when the solve stops at iteration 0).  Eight at a time,
-// every load of a group issued before its first store: one entry per pass (load, wait, store; the next load cannot move above a
-// store that might alias it) cost one HBM round trip per entry -- nine for a Cassie leg, ~10 us of a 150 us launch.
+// ik/ik/dls.cpp:71 clips the whole q after each step; no step is taken when the solve stops at iteration 0).
+// With the plan of the kernel arguments (chain_kernel_body.hpp PassPlan) which entries they are and their limits are wave-uniform
+// values of the argument segment: the per-lane loads of all of them are issued together (pass_plan_issue), then clamped and stored
+// (pass_plan_finish) -- one trip to memory.  hot_chain_body and hot_track_body issue the loads of their first never-stop solve
+// themselves, beside the ones of q0, the target and the sin / cos table.
+// Without a plan: sixteen entries at a time over the problem's tables in HBM, the loads of a group ahead of its first store (one entry
+// per pass -- load, wait, store; the next load cannot move above a store that might alias it -- cost one HBM round trip per entry).
+// The tables may alias q_out as far as the compiler knows, so their reads are VECTOR loads at wave-uniform addresses, and
+// `&& !a.q_in_chain[i]` is a branch per entry with a wait on its flag in front: the group's per-lane loads leave only behind the last
+// of those waits (a listing of the never-stop NJ = 7 kernel: fifteen dependent round trips, then one more for the loads).
 template <int NJ>
 IKD_FN void hot_pass_through_from(const ChainKernelArgs<NJ> &a, const double *q_src, double *q_out, int64_t b, bool stepped) {
     const ChainStrides st = chain_strides(a);
+    if (a.pass.state != 0) {
+        PassStage s;
+        pass_plan_issue(a, st, q_src, b, s);
+        pass_plan_finish(a, st, s, q_out, b, stepped);
+        return;
+    }
     constexpr int kGroup = 16;   // (a Cassie model's sixteen entries in ONE pass: with groups of eight the second group's loads waited
                                  // for the first group's stores -- a second HBM round trip in the prologue)
     for (int i0 = 0; i0 < a.nq; i0 += kGroup) {
         double v[kGroup], lo[kGroup], hi[kGroup];
         bool out[kGroup];
-        // (the wave-uniform reads in one batch, ahead of the per-lane loads: interleaved, each entry's three sat between two of those)
 #pragma unroll
         for (int k = 0; k < kGroup; ++k) {
             const int i = i0 + k < a.nq ? i0 + k : a.nq - 1;
@@ -626,12 +638,22 @@ IKD_FN void hot_chain_body(const ChainKernelArgs<NJ> &a, const Tab &t, int64_t g
     double q[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
-    double oMt[12];
-    load_target(a, b, oMt);
+    // (load_target in its two halves, the same expressions: the raw loads leave ahead of the plan's scalar reads)
+    double raw[12], oMt[12];
+    load_target_raw(a, a.targets, b, raw);
+    // never-stop, with a plan: the loads of the entries outside the chain travel with them too -- the prologue's one trip to memory
+    const bool planned = NEVERSTOP && a.pass.state != 0;
+    PassStage pass_stage;
+    if (NEVERSTOP) pass_plan_issue<true>(a, st, a.q0, b, pass_stage);   // (no branch among the prologue's loads: pass_plan_issue)
+    compose_target(a, raw, oMt);
     hot_lut_commit(t, lut_stage);
+    if (NEVERSTOP) pass_plan_settle(pass_stage);
     // The visitor never stops: every lane takes max_iterations steps, so what happens to the entries outside the support is
     // known before the loop -- copy them now (the stores drain while the loop runs) instead of after it (4 us of epilogue).
-    if (NEVERSTOP && valid) hot_pass_through(a, b, a.prm.max_iterations > 0);
+    if (NEVERSTOP && valid) {
+        if (planned) pass_plan_finish(a, st, pass_stage, a.q_out, b, a.prm.max_iterations > 0);
+        else hot_pass_through(a, b, a.prm.max_iterations > 0);
+    }
     int iters;
     bool success;
 #if defined(IKGPU_HOT_STAMP) && IKD_ON_DEVICE
@@ -681,6 +703,11 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
     double q[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) q[j] = a.q0[at(st.elem, st.q_prob, a.qidx[j], b)];
+    // (never-stop, with a plan: the first waypoint's loads of the entries outside the chain are issued here -- hot_chain_body; the later
+    // waypoints load theirs again, in front of their loop)
+    const bool planned = NEVERSTOP && a.pass.state != 0;
+    PassStage pass_stage;
+    if (NEVERSTOP) pass_plan_issue<true>(a, st, a.q0, b, pass_stage);
     // Order per waypoint: solve k, compose target k + 1 (its loads were issued before solve k began), store slab k, THEN issue the loads
     // of target k + 2.  The wait that consumes a prefetched target therefore never has a store of this waypoint in front of it (loads
     // and stores share one counter on gfx950: behind a store the wait would be for the store's acknowledgement, once per waypoint).
@@ -691,10 +718,12 @@ IKD_FN void hot_track_body(const ChainKernelArgs<NJ> &a, const Tab &t, int T, in
     }
     if (T > 1) load_target_raw(a, a.targets + t_slab, b, next);
     hot_lut_commit(t, lut_stage);
+    if (NEVERSTOP) pass_plan_settle(pass_stage);
     bool stepped = NEVERSTOP && a.prm.max_iterations > 0;   // (never-stop: every waypoint takes max_iterations steps, known here)
+    if (planned && valid && T > 0) pass_plan_finish(a, st, pass_stage, a.q_out, b, stepped);   // (ahead of the waypoint loop: the staged values end here)
     for (int k = 0; k < T; ++k) {
         double *q_out = a.q_out + k * q_slab;
-        if (NEVERSTOP && valid) hot_pass_through_to(a, q_out, b, stepped);   // the stores drain while the loop runs (hot_chain_body)
+        if (NEVERSTOP && valid && !(planned && k == 0)) hot_pass_through_to(a, q_out, b, stepped);   // the stores drain while the loop runs (hot_chain_body)
         int iters;
         bool success;
         hot_dls<NJ, S, NEVERSTOP>(t, a.prm, q, oMt, iters, success, any_active);   // (any_active by value: a fresh count per waypoint)

@@ -17,6 +17,24 @@ namespace ikdev {
 
 enum : int { LAYOUT_SOA = 0, LAYOUT_AOS = 1 };  // == ikgpu_layout
 
+// The entries of q OUTSIDE the chain as a plan carried in the kernel arguments: which they are and their limits, made once on the host
+// from the problem's own copies (kernels.hpp fill_pass_plan).  A body that finds one reads no flag and no limit from memory -- they are
+// wave-uniform values of the argument segment -- and issues the per-lane loads of every planned entry together, ahead of the first
+// store (pass_plan_issue / pass_plan_finish below).
+//   state == 0      no plan: a value-initialised ChainKernelArgs (the emulators and shims under tests/, the CPU oracle's fast path), more
+//                   than kPassPlanMax entries outside the chain, or IKGPU_PASS_PLAN=0.  The bodies walk q_in_chain / lower / upper.
+//   state == n + 1  n entries outside the chain, idx ascending; n == 0 (a chain that takes every entry of q, UR5) stores nothing.
+//                   Slots n .. kPassPlanMax - 1 repeat slot n - 1 (entry 0 when n == 0, as in a value-initialised plan), so a load
+//                   of any slot reads a valid address.
+// 328 bytes; ChainKernelArgs<7> is 680 bytes with it, ChainKernelArgs<6> 672 (352 / 344 without), and a hot kernel's argument
+// segment with its 984-byte table 1664 / 1656 bytes of the 4096 a launch may pass.
+constexpr int kPassPlanMax = 16;
+struct PassPlan {
+    int state;
+    int idx[kPassPlanMax];
+    double lo[kPassPlanMax], hi[kPassPlanMax];
+};
+
 template <int NJ>
 struct ChainKernelArgs {
     const ChainDesc<NJ> *desc;  // HBM copy of the chain table (uploaded at problem creation)
@@ -45,6 +63,7 @@ struct ChainKernelArgs {
     int leave_active, leave_after;
     int32_t *append_list;
     unsigned long long *append_count;
+    PassPlan pass;   // the entries of q outside the chain (above); last, so that a value-initialised struct has none
 };
 
 // First phase of a two-phase solve: the lanes of a wave whose problem is still open after the lock-step iterations append its index to
@@ -112,6 +131,74 @@ IKD_FN void load_target(const ChainKernelArgs<NJ> &a, int64_t b, double (&oMt)[1
     }
 }
 
+// ---- the entries of q outside the chain -------------------------------------------------------------------------------------------
+// dq = 0 there, so a solve only ever clips them to the limits (reference ik/ik/dls.cpp:71 clips the whole q after each step; no step is
+// taken when the solve stops at iteration 0): q_out = stepped ? min(hi, max(v, lo)) : v.
+// Through the plan (PassPlan above), in two halves so that a body can put other work between them: pass_plan_issue starts the per-lane
+// loads of every planned entry of column b of `src` -- nothing between them waits, and a plan without entries loads nothing --,
+// pass_plan_finish clamps and stores.  Both only with a plan (a.pass.state != 0).
+// Every slot is clamped in one straight run ahead of the stores, the spare slots too (they hold a copy of the last entry: loaded and
+// clamped with the others, never stored): the limits then come in by a few wide scalar loads, not by a pair per store with a wait each.
+struct PassStage {
+    double v[kPassPlanMax];
+};
+// ALWAYS: the loads are issued whatever the plan says (without entries every slot names entry 0, a valid address, and nothing of it
+// is stored).  For a prologue that has other loads in flight: a branch here would end the block they are scheduled in, and where its
+// two arms meet again every later wait is for the arm with fewer loads behind it -- on the other arm, for the plan's loads as well.
+template <bool ALWAYS = false, int NJ>
+IKD_FN void pass_plan_issue(const ChainKernelArgs<NJ> &a, const ChainStrides &st, const double *src, int64_t b, PassStage &s) {
+    if (ALWAYS || a.pass.state > 1) {
+#pragma unroll
+        for (int k = 0; k < kPassPlanMax; ++k) s.v[k] = src[at(st.elem, st.q_prob, a.pass.idx[k], b)];
+    }
+}
+// What a body that issued the loads ahead of other work calls in EVERY lane before its iteration loop: the loaded values are taken
+// here, whatever the plan says and whether or not the lane stores.  A load still in flight at the loop's entry on some path (a tail
+// lane, a plan without entries) costs the loop a wait of its own where its registers are first written.
+IKD_FN void pass_plan_settle(PassStage &s) {
+#pragma unroll
+    for (int k = 0; k < kPassPlanMax; ++k) IKD_PIN(s.v[k]);
+}
+template <int NJ>
+IKD_FN void pass_plan_finish(const ChainKernelArgs<NJ> &a, const ChainStrides &st, const PassStage &s, double *q_out, int64_t b, bool stepped) {
+    const int n = a.pass.state - 1;
+    if (n <= 0) return;
+    double w[kPassPlanMax];
+#pragma unroll
+    for (int k = 0; k < kPassPlanMax; ++k) {
+        double v = s.v[k];
+        IKD_PIN(v);   // the clamp stays HERE: moved up to the loads it would put their wait in front of whatever a body issues behind them
+        const double c = dmin(a.pass.hi[k], dmax(v, a.pass.lo[k]));
+        w[k] = stepped ? c : v;
+    }
+#pragma unroll
+    for (int k = 0; k < kPassPlanMax; ++k)
+        if (k < n) q_out[at(st.elem, st.q_prob, a.pass.idx[k], b)] = w[k];   // (wave-uniform test)
+}
+
+// The entries outside the chain of a solve started from column b of `src`, into q_out (a slab of its own for the jobs that have several).
+// With a plan every load is issued before the first store; without one, an entry per pass over the problem's tables in HBM.
+template <int NJ>
+IKD_FN void chain_pass_through_into(const ChainKernelArgs<NJ> &a, const double *src, double *q_out, int64_t b, bool stepped) {
+    const ChainStrides st = chain_strides(a);
+    if (a.pass.state != 0) {
+        PassStage s;
+        pass_plan_issue(a, st, src, b, s);
+        pass_plan_finish(a, st, s, q_out, b, stepped);
+        return;
+    }
+    for (int i = 0; i < a.nq; ++i) {
+        if (a.q_in_chain[i]) continue;
+        const double v = src[at(st.elem, st.q_prob, i, b)];
+        const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
+        q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
+    }
+}
+template <int NJ>
+IKD_FN void chain_pass_through_from(const ChainKernelArgs<NJ> &a, const double *src, int64_t b, bool stepped) {
+    chain_pass_through_into(a, src, a.q_out, b, stepped);
+}
+
 // B independent ik::dls() calls (reference ik/ik/dls.cpp:5-78), lane `gid`.
 template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>
 IKD_FN void dls_chain_body(const ChainKernelArgs<NJ> &a, const Desc &d, int64_t gid, AnyFn any_active) {
@@ -136,12 +223,7 @@ IKD_FN void dls_chain_body(const ChainKernelArgs<NJ> &a, const Desc &d, int64_t 
     for (int j = 0; j < NJ; ++j) a.q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
     // Entries outside the task support: dq = 0 there, so the loop only ever clamps them
     // (reference ik/ik/dls.cpp:71 clips the whole q after each step; no step is taken when iters == 0).
-    for (int i = 0; i < a.nq; ++i) {
-        if (a.q_in_chain[i]) continue;
-        const double v = a.q0[at(st.elem, st.q_prob, i, b)];
-        const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-        a.q_out[at(st.elem, st.q_prob, i, b)] = (iters > 0) ? c : v;
-    }
+    chain_pass_through_from(a, a.q0, b, iters > 0);
     if (a.success) a.success[b] = success ? 1 : 0;
     if (a.iters) a.iters[b] = iters;
 }
@@ -204,12 +286,7 @@ IKD_FN void dls_chain_track_body(const ChainKernelArgs<NJ> &a, const Desc &d, in
             for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
             if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
             if (a.iters) a.iters[k * a.B + b] = iters;
-            for (int i = 0; i < a.nq; ++i) {
-                if (a.q_in_chain[i]) continue;
-                const double v = a.q0[at(st.elem, st.q_prob, i, b)];
-                const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-                q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
-            }
+            chain_pass_through_into(a, a.q0, q_out, b, stepped);
         }
         if (k + 2 < T) load_target_raw(a, a.targets + (k + 2) * t_slab, b, next);
     }
@@ -266,12 +343,7 @@ IKD_FN int dls_chain_line_body(const ChainKernelArgs<NJ> &a, const Desc &d, cons
             for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
             if (a.success) a.success[k * a.B + b] = success ? 1 : 0;
             if (a.iters) a.iters[k * a.B + b] = iters;
-            for (int i = 0; i < a.nq; ++i) {
-                if (a.q_in_chain[i]) continue;
-                const double v = a.q0[at(st.elem, st.q_prob, i, b)];
-                const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-                q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
-            }
+            chain_pass_through_into(a, a.q0, q_out, b, stepped);
         }
         alive = alive && success;
         reached += alive ? 1 : 0;
@@ -329,12 +401,7 @@ IKD_FN int dls_chain_path_body(const ChainKernelArgs<NJ> &a, const Desc &d, cons
                 for (int j = 0; j < NJ; ++j) q_out[at(st.elem, st.q_prob, a.qidx[j], b)] = q[j];
                 if (a.success) a.success[n * a.B + b] = success ? 1 : 0;
                 if (a.iters) a.iters[n * a.B + b] = iters;
-                for (int i = 0; i < a.nq; ++i) {
-                    if (a.q_in_chain[i]) continue;
-                    const double v = a.q0[at(st.elem, st.q_prob, i, b)];
-                    const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-                    q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
-                }
+                chain_pass_through_into(a, a.q0, q_out, b, stepped);
             }
             alive = alive && success && !path_jumped<NJ>(q, q_prev, pa.max_joint_step);
             reached += alive ? 1 : 0;
@@ -401,18 +468,6 @@ IKD_FN void multistart_store(const ChainKernelArgs<NJ> &a, const MultistartArgs 
     if (a.iters) a.iters[b] = iters;
     if (ms.winner) ms.winner[b] = k;
     if (ms.err_sq) ms.err_sq[b] = err_sq;
-}
-
-// Entries outside the task support of a solve started from column b of `src`: clipped once a step was taken (dls_chain_body).
-template <int NJ>
-IKD_FN void chain_pass_through_from(const ChainKernelArgs<NJ> &a, const double *src, int64_t b, bool stepped) {
-    const ChainStrides st = chain_strides(a);
-    for (int i = 0; i < a.nq; ++i) {
-        if (a.q_in_chain[i]) continue;
-        const double v = src[at(st.elem, st.q_prob, i, b)];
-        const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-        a.q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
-    }
 }
 
 template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn, class Exchange>
@@ -683,18 +738,6 @@ IKD_FN void dls_chain_goalset_body(const ChainKernelArgs<NJ> &a, const GoalsetAr
 // gid >> log2K with start gid & (K - 1)) and the greedy rule of device/solutions.hpp over their results: start k is kept when it met the
 // stop rule, fewer than N are kept, and some chain entry differs by sep or more from every start kept before it.  Three pieces again: the
 // lane's own solve, the K steps of the set (solutions_offer / solutions_take) and a kept lane's stores (solutions_store).
-
-// Entries outside the task support of a solve started from column b of `src`, into a slab of its own (chain_pass_through_from).
-template <int NJ>
-IKD_FN void chain_pass_through_into(const ChainKernelArgs<NJ> &a, const double *src, double *q_out, int64_t b, bool stepped) {
-    const ChainStrides st = chain_strides(a);
-    for (int i = 0; i < a.nq; ++i) {
-        if (a.q_in_chain[i]) continue;
-        const double v = src[at(st.elem, st.q_prob, i, b)];
-        const double c = dmin(a.upper[i], dmax(v, a.lower[i]));
-        q_out[at(st.elem, st.q_prob, i, b)] = stepped ? c : v;
-    }
-}
 
 // One start: the single solve's loop, unchanged.  (Only converged starts matter: no evaluation after it.)
 template <int NJ, int KT, int SMASK = -1, class Desc, class AnyFn>

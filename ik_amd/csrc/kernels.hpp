@@ -348,6 +348,8 @@ inline void fill_chain_kernel_args(A &a, const ProblemHost &ph, const DeviceTabl
     fill_chain_args(ph, a.ref_pl, a.qidx, a.vidx, &a.nq, &a.nv, &a.prm.priority, &a.prm.idmask, &a.prm.unit_weights);
     a.desc = reinterpret_cast<decltype(a.desc)>(dt.chain_desc);
     a.lower = dt.lower; a.upper = dt.upper; a.q_in_chain = dt.q_in_chain;
+    // the entries outside the chain once more, as values of the argument segment (ikdev::PassPlan): what the tables above hold in HBM
+    a.pass.state = fill_pass_plan(ph, static_cast<int>(sizeof(a.pass.idx) / sizeof(a.pass.idx[0])), a.pass.idx, a.pass.lo, a.pass.hi);
 }
 // Run-time compiled hot build (rtc.cpp): dls_chain_hot_kernel<NJ, code...> for THIS chain's structure code through hipRTC.
 // available(compile = false): would it be attempted (libhiprtc loads, not disabled); (compile = true): compiled and loaded, or cached.

@@ -687,6 +687,30 @@ void fill_chain_args(const ProblemHost &ph, double *ref_pl12, int *qidx, int *vi
     *unit_weights = task_has_unit_weights(ph.tasks[0]) ? 1 : 0;
 }
 
+int fill_pass_plan(const ProblemHost &ph, int max_entries, int *idx, double *lo, double *hi) {
+    const char *env = std::getenv("IKGPU_PASS_PLAN");
+    if (env && std::strcmp(env, "0") == 0) return 0;   // A/B switch: the bodies walk the tables in HBM
+    const size_t nq = static_cast<size_t>(ph.nq);
+    if (ph.q_in_chain.size() != nq || ph.lower.size() != nq || ph.upper.size() != nq) return 0;
+    int n = 0;
+    for (size_t i = 0; i < nq; ++i) n += ph.q_in_chain[i] ? 0 : 1;
+    if (n > max_entries) return 0;
+    int k = 0;
+    for (size_t i = 0; i < nq; ++i) {
+        if (ph.q_in_chain[i]) continue;
+        idx[k] = static_cast<int>(i);
+        lo[k] = ph.lower[i];
+        hi[k] = ph.upper[i];
+        ++k;
+    }
+    for (; k < max_entries; ++k) {   // the spare slots repeat the last entry: a load of any slot reads a valid address
+        idx[k] = n > 0 ? idx[n - 1] : 0;
+        lo[k] = n > 0 ? lo[n - 1] : 0.0;
+        hi[k] = n > 0 ? hi[n - 1] : 0.0;
+    }
+    return n + 1;
+}
+
 TreeArgsHost tree_args(const ProblemHost &ph) {
     TreeArgsHost a{};
     for (int j = 0; j < kMaxChain; ++j) {

@@ -142,6 +142,10 @@ std::vector<double> tree_desc_table(const ProblemHost &ph);
 // The per-problem scalars of ikdev::ChainKernelArgs<nj>.
 void fill_chain_args(const ProblemHost &ph, double *ref_pl12, int *qidx, int *vidx, int *nq, int *nv, int *priority,
                      int *idmask, int *unit_weights);
+// ... and its plan of the entries of q outside the chain (device/chain_kernel_body.hpp ikdev::PassPlan: idx, lo, hi of max_entries slots),
+// from the problem's own q_in_chain, lower and upper.  Returns PassPlan::state: the number of entries + 1, or 0 for "no plan" -- more
+// entries outside the chain than the plan holds, or IKGPU_PASS_PLAN=0 in the environment of this call (an A/B switch).
+int fill_pass_plan(const ProblemHost &ph, int max_entries, int *idx, double *lo, double *hi);
 // Bit j set when placement j of the chain has an exactly-identity rotation; bit nj for the frame placement.
 int chain_identity_mask(const ChainHost &c);
 // ... and what fill_chain_args hands the kernels as LoopParams::idmask: that mask, and ChainHost::prismatic from bit 16 up
