@@ -70,92 +70,56 @@ __global__ __launch_bounds__(kBlock) void dls_chain_refill_kernel(const ChainKer
     ikdev::dls_chain_refill_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, queue, chunk);
 }
 
-// T chained solves per problem in one launch (device/chain_kernel_body.hpp dls_chain_track_body): the general build's tracking kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_track_kernel(const ChainKernelArgs<NJ> a, const int T) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+// The lock-step jobs of kernels.hpp IKGPU_CHAIN_JOBS on the general build, one overload per tail argument: the job's lane program
+// (device/chain_kernel_body.hpp) on lane gid -- one wave64 per workgroup -- with the chain table read by scalar loads from HBM, as
+// dls_chain_kernel reads it, and what the program takes besides its tail.
+#define IKGPU_JOB_KERNEL(TAIL)         \
+    template <int NJ, int KT, int SMASK> \
+    __global__ __launch_bounds__(kBlock) void dls_chain_job_kernel(const ChainKernelArgs<NJ> a, const TAIL)
+#define IKGPU_JOB_LANE                                                                   \
+    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;         \
+    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;
+IKGPU_JOB_KERNEL(int T) {
+    IKGPU_JOB_LANE
     ikdev::dls_chain_track_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, T, gid, ikdev::KeepGoing{0, 0, 0});
 }
-
-// A straight Cartesian line to one goal per problem in one launch (device/chain_kernel_body.hpp dls_chain_line_body): the general build's
-// line kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_line_kernel(const ChainKernelArgs<NJ> a, const ikdev::LineArgs la) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+IKGPU_JOB_KERNEL(ikdev::MultistartArgs ms) {
+    IKGPU_JOB_LANE
+    ikdev::dls_chain_multistart_body<NJ, KT, SMASK>(a, ms, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
+}
+IKGPU_JOB_KERNEL(ikdev::SolutionsArgs sa) {
+    IKGPU_JOB_LANE
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    ikdev::dls_chain_solutions_body<NJ, KT, SMASK>(a, sa, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0},
+                                                   ikdev::SolutionsShuffle{lane & ~((1 << sa.ms.log2K) - 1)});
+}
+IKGPU_JOB_KERNEL(ikdev::LineArgs la) {
+    IKGPU_JOB_LANE
     (void)ikdev::dls_chain_line_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, la, gid, ikdev::KeepGoing{0, 0, 0});
 }
-
-// The waypoints of ikgpu_line_targets for a chain problem: a.targets holds the goals, a.oMf_out the T slabs.
-// KINDS: the chain has a prismatic joint (device/chain_solver.hpp kKindShift), here and in the stage kernels below.
-template <int NJ, bool KINDS>
-__global__ __launch_bounds__(kBlock) void line_targets_chain_kernel(const ChainKernelArgs<NJ> a, const int T) {
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (b >= a.B) return;
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;
-    double q[NJ], goal[12];
-    ikdev::line_load(a, b, q, goal);
-    ikdev::LineStart ls;
-    ikdev::line_chain_start<KINDS>(a, *(ConstDesc *)a.desc, q, goal, ls);
-    for (int k = 0; k < T; ++k) {
-        double t[12];
-        ikdev::line_waypoint(ls, goal, k, T, t);
-        double *out = a.oMf_out + static_cast<int64_t>(k) * 12 * a.B;
-#pragma unroll
-        for (int c = 0; c < 12; ++c) out[ikdev::at(a.layout, a.B, 12, c, b)] = t[c];
-    }
+IKGPU_JOB_KERNEL(ikdev::GoalsetArgs ga) {
+    IKGPU_JOB_LANE
+    ikdev::dls_chain_goalset_body<NJ, KT, SMASK>(a, ga, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{},
+                                                 ikdev::GoalsetBallot{});
 }
-
-struct LineTargetsArgs {
-    const double *ref_pl, *goals;
-    double *out;
-    int64_t B;
-    int ntasks, T, layout;
-};
-__global__ __launch_bounds__(256) void line_targets_from_fk_kernel(const LineTargetsArgs a) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= a.B * a.ntasks) return;
-    const int64_t b = i % a.B;
-    const int s = static_cast<int>(i / a.B);
-    double f[12], goal[12], ref[12];
-#pragma unroll
-    for (int c = 0; c < 12; ++c) {
-        const int64_t at = ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b);
-        f[c] = a.out[at];   // slab 0: oMf(q0) of this slot, read before waypoint 0 goes over it
-        goal[c] = a.goals[at];
-        ref[c] = a.ref_pl[s * 12 + c];
-    }
-    const double Rf[9] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]}, pf[3] = {f[9], f[10], f[11]};
-    ikdev::LineStart ls;
-    ikdev::line_start(ref, Rf, pf, goal, ls);
-    for (int k = 0; k < a.T; ++k) {
-        double t[12];
-        ikdev::line_waypoint(ls, goal, k, a.T, t);
-        double *out = a.out + static_cast<int64_t>(k) * a.ntasks * 12 * a.B;
-#pragma unroll
-        for (int c = 0; c < 12; ++c) out[ikdev::at(a.layout, a.B, a.ntasks * 12, s * 12 + c, b)] = t[c];
-    }
-}
-
-__global__ __launch_bounds__(256) void line_reached_kernel(int64_t B, int T, const uint8_t *success, int32_t *reached) {
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (b >= B) return;
-    int n = 0;
-    while (n < T && success[n * B + b]) ++n;
-    reached[b] = n;
-}
-
-// A Cartesian path through P vias per problem with the joint-step rule in one launch (device/chain_kernel_body.hpp dls_chain_path_body):
-// the general build's path kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_path_kernel(const ChainKernelArgs<NJ> a, const ikdev::PathArgs pa) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
+IKGPU_JOB_KERNEL(ikdev::PathArgs pa) {
+    IKGPU_JOB_LANE
     (void)ikdev::dls_chain_path_body<NJ, KT, SMASK>(a, *(ConstDesc *)a.desc, pa, gid, ikdev::KeepGoing{0, 0, 0});
 }
+IKGPU_JOB_KERNEL(ikdev::PickArgs pk) {
+    IKGPU_JOB_LANE
+    ikdev::dls_chain_pick_body<NJ, KT, SMASK>(a, pk, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
+}
+IKGPU_JOB_KERNEL(ikdev::PathMultistartArgs pm) {
+    IKGPU_JOB_LANE
+    ikdev::dls_chain_path_multistart_body<NJ, KT, SMASK>(a, pm, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
+}
+#undef IKGPU_JOB_LANE
+#undef IKGPU_JOB_KERNEL
 
-// The waypoints of ikgpu_path_targets for a chain problem: a.targets holds the P slabs of vias, a.oMf_out the P x T slabs.
+// The waypoints of ikgpu_path_targets for a chain problem: a.targets holds the P slabs of vias, a.oMf_out the P x T slabs.  P = 1 is
+// ikgpu_line_targets: one goal, T slabs.
+// KINDS: the chain has a prismatic joint (device/chain_solver.hpp kKindShift), here and in the stage kernels below.
 template <int NJ, bool KINDS>
 __global__ __launch_bounds__(kBlock) void path_targets_chain_kernel(const ChainKernelArgs<NJ> a, const int P, const int T) {
     const int64_t b = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -244,54 +208,6 @@ __global__ __launch_bounds__(256) void path_reached_kernel(const PathReached r) 
     r.reached[b] = n;
 }
 
-// K starts per problem in one launch, the best one stored (device/chain_kernel_body.hpp dls_chain_multistart_body): the general build's
-// multi-start kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_multistart_kernel(const ChainKernelArgs<NJ> a, const ikdev::MultistartArgs ms) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
-    ikdev::dls_chain_multistart_body<NJ, KT, SMASK>(a, ms, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
-}
-
-// K starts per problem in one launch, the converged one with the smallest cost stored (device/chain_kernel_body.hpp dls_chain_pick_body):
-// the general build's pick kernel, one instantiation for the four rules.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_pick_kernel(const ChainKernelArgs<NJ> a, const ikdev::PickArgs pk) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
-    ikdev::dls_chain_pick_body<NJ, KT, SMASK>(a, pk, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
-}
-
-// K starts per problem in one launch against via 0, each scouting the path behind it, the one that gets furthest stored
-// (device/chain_kernel_body.hpp dls_chain_path_multistart_body): the general build's path multi-start kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_path_multistart_kernel(const ChainKernelArgs<NJ> a, const ikdev::PathMultistartArgs pm) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
-    ikdev::dls_chain_path_multistart_body<NJ, KT, SMASK>(a, pm, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{});
-}
-
-// K starts per problem in one launch, the distinct converged ones stored (device/chain_kernel_body.hpp dls_chain_solutions_body): the
-// general build's solution-set kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_solutions_kernel(const ChainKernelArgs<NJ> a, const ikdev::SolutionsArgs sa) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / K whole problems
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
-    const int lane = static_cast<int>(threadIdx.x) & 63;
-    ikdev::dls_chain_solutions_body<NJ, KT, SMASK>(a, sa, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0},
-                                                   ikdev::SolutionsShuffle{lane & ~((1 << sa.ms.log2K) - 1)});
-}
-
-// G goals and K starts per problem in one launch, the best candidate stored (device/chain_kernel_body.hpp dls_chain_goalset_body): the
-// general build's goal-set kernel.
-template <int NJ, int KT, int SMASK>
-__global__ __launch_bounds__(kBlock) void dls_chain_goalset_kernel(const ChainKernelArgs<NJ> a, const ikdev::GoalsetArgs ga) {
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;   // one wave64 per workgroup: 64 / (G x K) whole problems
-    typedef const IKD_CONST_AS ChainDesc<NJ> ConstDesc;   // scalar loads from HBM, as dls_chain_kernel
-    ikdev::dls_chain_goalset_body<NJ, KT, SMASK>(a, ga, *(ConstDesc *)a.desc, gid, ikdev::KeepGoing{0, 0, 0}, ikdev::MultistartShuffle{},
-                                                 ikdev::GoalsetBallot{});
-}
-
 struct MultistartStartsArgs {
     const double *q0, *lower, *upper;
     const uint8_t *draw;
@@ -312,7 +228,12 @@ __global__ __launch_bounds__(256) void multistart_starts_kernel(const Multistart
     }
 }
 
-__global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m) {
+// One step of a best-of-K definition run as a loop (kernels.hpp MultistartMerge), one thread per problem: start k's squared error, its
+// rank key_of(b, err) against the best so far (a tie keeps the lower index), and when it wins its q / success / iters / index / error
+// into the caller's outputs, then won(b) for what the job stores besides.  A thread calls key_of exactly once, and before won: a job
+// may keep what key_of read for won (path_multistart_merge's `reached`).
+template <class KeyOf, class Won>
+__device__ __forceinline__ void merge_step(const MultistartMerge &m, KeyOf key_of, Won won) {
     const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (b >= m.B) return;
     double err = 0.0;
@@ -320,7 +241,7 @@ __global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m)
         const double e = m.e[ikdev::at(m.layout, m.B, m.M, r, b)];
         err = ikdev::dfma(e, e, err);
     }
-    const unsigned long long key = ikdev::multistart_key(m.success[b] != 0, err);
+    const unsigned long long key = key_of(b, err);
     if (m.k > 0 && !(key < m.key[b])) return;   // (a tie keeps the lower index)
     m.key[b] = key;
     for (int i = 0; i < m.nq; ++i) m.q_out[ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
@@ -328,6 +249,11 @@ __global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m)
     if (m.iters_out) m.iters_out[b] = m.iters[b];
     if (m.winner) m.winner[b] = m.k;
     if (m.err_sq) m.err_sq[b] = err;
+    won(b);
+}
+
+__global__ __launch_bounds__(256) void multistart_merge(const MultistartMerge m) {
+    merge_step(m, [&](int64_t b, double err) { return ikdev::multistart_key(m.success[b] != 0, err); }, [](int64_t) {});
 }
 
 // The cost of one start's result (device/pick.hpp), one thread per problem: the support entries in increasing index; MANIPULABILITY
@@ -373,46 +299,18 @@ __global__ __launch_bounds__(256) void pick_cost_kernel(const PickCost c) {
 }
 
 __global__ __launch_bounds__(256) void pick_merge(const PickMerge p) {
-    const MultistartMerge &m = p.m;
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (b >= m.B) return;
-    double err = 0.0;
-    for (int r = 0; r < m.M; ++r) {
-        const double e = m.e[ikdev::at(m.layout, m.B, m.M, r, b)];
-        err = ikdev::dfma(e, e, err);
-    }
-    const unsigned long long key = ikdev::pick_key(m.success[b] != 0, p.cost[b], err);
-    if (m.k > 0 && !(key < m.key[b])) return;   // (a tie keeps the lower index)
-    m.key[b] = key;
-    for (int i = 0; i < m.nq; ++i) m.q_out[ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
-    if (m.success_out) m.success_out[b] = m.success[b];
-    if (m.iters_out) m.iters_out[b] = m.iters[b];
-    if (m.winner) m.winner[b] = m.k;
-    if (m.err_sq) m.err_sq[b] = err;
-    if (p.cost_out) p.cost_out[b] = p.cost[b];
+    merge_step(p.m, [&](int64_t b, double err) { return ikdev::pick_key(p.m.success[b] != 0, p.cost[b], err); },
+               [&](int64_t b) { if (p.cost_out) p.cost_out[b] = p.cost[b]; });
 }
 
 __global__ __launch_bounds__(256) void path_multistart_merge(const PathMultistartMerge p) {
-    const MultistartMerge &m = p.m;
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (b >= m.B) return;
-    double err = 0.0;
-    for (int r = 0; r < m.M; ++r) {
-        const double e = m.e[ikdev::at(m.layout, m.B, m.M, r, b)];
-        err = ikdev::dfma(e, e, err);
-    }
-    const bool entered = m.success[b] != 0;
-    const int reached = !entered ? -1 : p.reached_k ? p.reached_k[b] : 0;
-    if (p.reached_all) p.reached_all[static_cast<int64_t>(m.k) * m.B + b] = reached;
-    const unsigned long long key = ikdev::pick_key(entered, static_cast<double>(p.N - (entered ? reached : 0)), err);
-    if (m.k > 0 && !(key < m.key[b])) return;   // (a tie keeps the lower index)
-    m.key[b] = key;
-    for (int i = 0; i < m.nq; ++i) m.q_out[ikdev::at(m.layout, m.B, m.nq, i, b)] = m.q[ikdev::at(m.layout, m.B, m.nq, i, b)];
-    if (m.success_out) m.success_out[b] = m.success[b];
-    if (m.iters_out) m.iters_out[b] = m.iters[b];
-    if (m.winner) m.winner[b] = m.k;
-    if (m.err_sq) m.err_sq[b] = err;
-    if (p.reached_out) p.reached_out[b] = entered ? reached : 0;
+    int reached = 0;   // of the path after via 0 by start k; -1 in reached_all's row for a start whose entry failed
+    merge_step(p.m, [&](int64_t b, double err) {
+        const bool entered = p.m.success[b] != 0;
+        reached = entered && p.reached_k ? p.reached_k[b] : 0;
+        if (p.reached_all) p.reached_all[static_cast<int64_t>(p.m.k) * p.m.B + b] = entered ? reached : -1;
+        return ikdev::pick_key(entered, static_cast<double>(p.N - reached), err);
+    }, [&](int64_t b) { if (p.reached_out) p.reached_out[b] = reached; });
 }
 
 __global__ __launch_bounds__(256) void goalset_reachable_kernel(int64_t B, bool first, const uint8_t *success, uint8_t *reachable) {
@@ -494,6 +392,13 @@ ChainKernelArgs<NJ> make_args(const ProblemHost &ph, const DeviceTables &dt) {
 
 inline dim3 grid_for(int64_t B) { return dim3(static_cast<unsigned>((B + kBlock - 1) / kBlock)); }
 
+// A launch of one of the small kernels around the solves: n threads in blocks of 256.
+template <class... P, class... A>
+hipError_t launch_flat(void (*kernel)(P...), int64_t n, hipStream_t stream, const A &...args) {
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, args...);
+    return hipGetLastError();
+}
+
 // One build of the chain kernel (SM: its compile-time placement mask and weights) in the stop-rule mode the batch asks for.
 template <int NJ, int KT, int SM>
 hipError_t run_dls_build(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm, hipStream_t stream,
@@ -537,20 +442,11 @@ hipError_t run_dls(const ProblemHost &ph, const DeviceTables &dt, const BatchIO 
     return with_chain_build<NJ>(a.prm.idmask, a.prm.unit_weights != 0, [&](auto smask) -> hipError_t {
         constexpr int SM = decltype(smask)::value;
         if (job.kind == ChainJob::Solve) return run_dls_build<NJ, KT, SM>(ph, dt, io, prm, stream, a);
-        const dim3 grid = grid_for(job.lanes(io.B));
-        if ((job.kind == ChainJob::Solutions || job.kind == ChainJob::Line || job.kind == ChainJob::Path || job.kind == ChainJob::Pick ||
-             job.kind == ChainJob::PathMultistart) && prm.stop_sq_tol < 0.0)
-            return hipErrorInvalidValue;
-        if (job.kind == ChainJob::PathMultistart)
-            hipLaunchKernelGGL((dls_chain_path_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.pms);
-        else if (job.kind == ChainJob::Pick) hipLaunchKernelGGL((dls_chain_pick_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.pick);
-        else if (job.kind == ChainJob::Path) hipLaunchKernelGGL((dls_chain_path_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.path);
-        else if (job.kind == ChainJob::Line) hipLaunchKernelGGL((dls_chain_line_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.line);
-        else if (job.kind == ChainJob::Track) hipLaunchKernelGGL((dls_chain_track_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.T);
-        else if (job.kind == ChainJob::Solutions) hipLaunchKernelGGL((dls_chain_solutions_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.sol);
-        else if (job.kind == ChainJob::Goalset) hipLaunchKernelGGL((dls_chain_goalset_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.goal);
-        else hipLaunchKernelGGL((dls_chain_multistart_kernel<NJ, KT, SM>), grid, dim3(kBlock), 0, stream, a, job.ms);
-        return hipGetLastError();
+        return with_chain_job(job, prm.stop_sq_tol < 0.0, [&](auto rule, auto) -> hipError_t {
+            // (the overload of dls_chain_job_kernel that takes the job's tail)
+            hipLaunchKernelGGL((dls_chain_job_kernel<NJ, KT, SM>), grid_for(job.lanes(io.B)), dim3(kBlock), 0, stream, a, decltype(rule)::tail(job));
+            return hipGetLastError();
+        });
     });
 }
 
@@ -611,9 +507,7 @@ __global__ __launch_bounds__(256) void targets_from_pose7_kernel(int64_t B, int 
 }  // namespace
 
 hipError_t launch_targets_from_pose7(int64_t B, int ntasks, const double *pose7, double *targets12, int layout, hipStream_t stream) {
-    const int64_t n = B * ntasks;
-    hipLaunchKernelGGL(targets_from_pose7_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, B, ntasks, pose7, targets12, layout);
-    return hipGetLastError();
+    return launch_flat(targets_from_pose7_kernel, B * ntasks, stream, B, ntasks, pose7, targets12, layout);
 }
 
 bool refill_wanted(const ikgpu_dls_params &prm, int64_t B, int64_t resident_waves) {
@@ -698,8 +592,7 @@ hipError_t launch_chain_pass_through(const ProblemHost &ph, const DeviceTables &
     for (uint8_t in : ph.q_in_chain) any_outside = any_outside || !in;
     if (!any_outside) return hipSuccess;
     const PassThroughArgs p{io.q0, dt.lower, dt.upper, dt.q_in_chain, iters, io.q_out, io.B, ph.nq, io.layout};
-    hipLaunchKernelGGL(chain_pass_through_kernel, dim3(static_cast<unsigned>((io.B + 255) / 256)), dim3(256), 0, stream, p);
-    return hipGetLastError();
+    return launch_flat(chain_pass_through_kernel, io.B, stream, p);
 }
 
 bool chain_shape_built(int nj, int type) {
@@ -721,33 +614,19 @@ hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const
     not_built(nj, type);
 }
 
+// (the path kernels with one segment; launch_line_reached: with no joint-step rule, so that q0 / q_traj / support are never read)
 hipError_t launch_line_targets_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, int T, const double *q0, const double *goals,
                                      double *out, int layout, hipStream_t stream) {
-    const int nj = ph.chain.nj;
-#define X(N)                                                                                                 \
-    if (nj == N) {                                                                                           \
-        ChainKernelArgs<N> a = make_args<N>(ph, dt);                                                         \
-        a.layout = layout; a.B = B; a.q0 = q0; a.targets = goals; a.oMf_out = out;                           \
-        if (ph.chain.prismatic) hipLaunchKernelGGL((line_targets_chain_kernel<N, true>), grid_for(B), dim3(kBlock), 0, stream, a, T); \
-        else hipLaunchKernelGGL((line_targets_chain_kernel<N, false>), grid_for(B), dim3(kBlock), 0, stream, a, T); \
-        return hipGetLastError();                                                                            \
-    }
-    IKGPU_FOR_NJ(X)
-#undef X
-    not_built(nj, 0);
+    return launch_path_targets_chain(ph, dt, B, 1, T, q0, goals, out, layout, stream);
 }
 
 hipError_t launch_line_targets_from_fk(int64_t B, int ntasks, int T, const double *ref_pl, const double *goals, double *out, int layout,
                                        hipStream_t stream) {
-    const LineTargetsArgs a{ref_pl, goals, out, B, ntasks, T, layout};
-    const int64_t n = B * ntasks;
-    hipLaunchKernelGGL(line_targets_from_fk_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    return launch_path_targets_from_fk(B, ntasks, 1, T, ref_pl, goals, out, layout, stream);
 }
 
 hipError_t launch_line_reached(int64_t B, int T, const uint8_t *success, int32_t *reached, hipStream_t stream) {
-    hipLaunchKernelGGL(line_reached_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, T, success, reached);
-    return hipGetLastError();
+    return launch_path_reached(PathReached{B, 0, T, 0, 0.0, nullptr, success, nullptr, nullptr, reached}, stream);
 }
 
 hipError_t launch_path_targets_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, int P, int T, const double *q0, const double *vias,
@@ -768,59 +647,29 @@ hipError_t launch_path_targets_chain(const ProblemHost &ph, const DeviceTables &
 
 hipError_t launch_path_targets_from_fk(int64_t B, int ntasks, int P, int T, const double *ref_pl, const double *vias, double *out, int layout,
                                        hipStream_t stream) {
-    const PathTargetsArgs a{ref_pl, vias, out, B, ntasks, P, T, layout};
-    const int64_t n = B * ntasks;
-    hipLaunchKernelGGL(path_targets_from_fk_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    return launch_flat(path_targets_from_fk_kernel, B * ntasks, stream, PathTargetsArgs{ref_pl, vias, out, B, ntasks, P, T, layout});
 }
 
-hipError_t launch_path_reached(const PathReached &r, hipStream_t stream) {
-    hipLaunchKernelGGL(path_reached_kernel, dim3(static_cast<unsigned>((r.B + 255) / 256)), dim3(256), 0, stream, r);
-    return hipGetLastError();
-}
+hipError_t launch_path_reached(const PathReached &r, hipStream_t stream) { return launch_flat(path_reached_kernel, r.B, stream, r); }
 
 hipError_t launch_multistart_starts(const DeviceTables &dt, int nq, int64_t B, int k0, int k1, const double *q0, uint64_t seed, double *out,
                                     int layout, hipStream_t stream) {
     if (k1 <= k0 || B <= 0) return hipSuccess;
-    const MultistartStartsArgs a{q0, dt.lower, dt.upper, dt.draw, out, seed, B, nq, layout, k0, k1};
-    const int64_t n = B * (k1 - k0);
-    hipLaunchKernelGGL(multistart_starts_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    return launch_flat(multistart_starts_kernel, B * (k1 - k0), stream, MultistartStartsArgs{q0, dt.lower, dt.upper, dt.draw, out, seed, B, nq, layout, k0, k1});
 }
 
-hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream) {
-    hipLaunchKernelGGL(multistart_merge, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
-    return hipGetLastError();
-}
-
-hipError_t launch_pick_cost(const PickCost &c, hipStream_t stream) {
-    hipLaunchKernelGGL(pick_cost_kernel, dim3(static_cast<unsigned>((c.B + 255) / 256)), dim3(256), 0, stream, c);
-    return hipGetLastError();
-}
-
-hipError_t launch_pick_merge(const PickMerge &m, hipStream_t stream) {
-    hipLaunchKernelGGL(pick_merge, dim3(static_cast<unsigned>((m.m.B + 255) / 256)), dim3(256), 0, stream, m);
-    return hipGetLastError();
-}
-
-hipError_t launch_path_multistart_merge(const PathMultistartMerge &m, hipStream_t stream) {
-    hipLaunchKernelGGL(path_multistart_merge, dim3(static_cast<unsigned>((m.m.B + 255) / 256)), dim3(256), 0, stream, m);
-    return hipGetLastError();
-}
+hipError_t launch_multistart_merge(const MultistartMerge &m, hipStream_t stream) { return launch_flat(multistart_merge, m.B, stream, m); }
+hipError_t launch_pick_cost(const PickCost &c, hipStream_t stream) { return launch_flat(pick_cost_kernel, c.B, stream, c); }
+hipError_t launch_pick_merge(const PickMerge &m, hipStream_t stream) { return launch_flat(pick_merge, m.m.B, stream, m); }
+hipError_t launch_path_multistart_merge(const PathMultistartMerge &m, hipStream_t stream) { return launch_flat(path_multistart_merge, m.m.B, stream, m); }
+hipError_t launch_solutions_insert(const SolutionsInsert &m, hipStream_t stream) { return launch_flat(solutions_insert, m.B, stream, m); }
 
 hipError_t launch_goalset_reachable(int64_t B, bool first, const uint8_t *success, uint8_t *reachable, hipStream_t stream) {
-    hipLaunchKernelGGL(goalset_reachable_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, first, success, reachable);
-    return hipGetLastError();
+    return launch_flat(goalset_reachable_kernel, B, stream, B, first, success, reachable);
 }
 
 hipError_t launch_goalset_split(int64_t B, int K, const int32_t *winner, int32_t *goal, int32_t *start, hipStream_t stream) {
-    hipLaunchKernelGGL(goalset_split_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, stream, B, K, winner, goal, start);
-    return hipGetLastError();
-}
-
-hipError_t launch_solutions_insert(const SolutionsInsert &m, hipStream_t stream) {
-    hipLaunchKernelGGL(solutions_insert, dim3(static_cast<unsigned>((m.B + 255) / 256)), dim3(256), 0, stream, m);
-    return hipGetLastError();
+    return launch_flat(goalset_split_kernel, B, stream, B, K, winner, goal, start);
 }
 
 hipError_t launch_eval_chain(const ProblemHost &ph, const DeviceTables &dt, int64_t B, const double *q,

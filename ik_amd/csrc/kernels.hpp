@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -70,49 +71,100 @@ struct BatchIO {
 };
 
 // What a launch of the chain kernel is asked for, in the build the problem's single solve takes (general / hot / run-time compiled
-// hot), so that every kind returns the single solve's bits:
-//   Solve:      one solve per problem, in the stop-rule mode the batch asks for (run_stop_rule).
-//   Track:      T chained solves per problem in ONE launch, q on-chip between them (ikgpu_dls_track_batch; device/chain_kernel_body.hpp
+// hot), so that every kind returns the single solve's bits.  Solve is one solve per problem, in the stop-rule mode the batch asks
+// for (run_stop_rule).  Every other job is ONE lock-step launch of a kernel that takes (a, t) and the job's own tail argument: no LDS
+// beyond the hot program's sin / cos table, no queue slot, no worklist, no allocation, so the launch is capturable.  What a launcher
+// knows of such a job is its row below -- the tail's type and its member of ChainJob, the lanes a problem takes, and whether the job
+// exists without a stop rule.  Each build then states the job once more, as the call of its lane program: the overload of
+// dls_chain_job_kernel (kernels.hip) and of dls_chain_hot_job_kernel (kernels_hot.hip) that takes the job's tail, and the job's row of
+// kHotRows (rtc.cpp).
+//   Track:      T chained solves per problem, q on-chip between them (ikgpu_dls_track_batch; device/chain_kernel_body.hpp
 //               dls_chain_track_body, device/chain_hot.hpp hot_track_body): `io` holds the pointers of waypoint 0, waypoint k's slab of
 //               targets / q_out / success / iters follows at k times the slab's size.
-//   Multistart: K = 1 << ms.log2K starts per problem in ONE launch, the best one stored (ikgpu_dls_multistart_batch;
-//               dls_chain_multistart_body, hot_multistart_body): B x K lanes, problem gid / K with start gid % K.
+//   Multistart: K = 1 << ms.log2K starts per problem, the best one stored (ikgpu_dls_multistart_batch; dls_chain_multistart_body,
+//               hot_multistart_body): B x K lanes, problem gid / K with start gid % K -- one wave serves 64 / K whole problems.
 //   Solutions:  the same B x K lanes, the distinct converged starts stored, up to sol.N per problem (ikgpu_dls_solutions_batch;
 //               dls_chain_solutions_body, hot_solutions_body): `io.q_out` / `io.iters` are [N] slabs, `io.success` is not written.  Needs a
-//               stop rule (the never-stop visitor converges nowhere): a launcher refuses the job without one.
-//   Line:       T chained solves per problem in ONE launch along the straight line from the pose at q0 to the problem's goal
-//               (ikgpu_dls_line_batch; dls_chain_line_body, hot_line_body): `io.targets` holds ONE goal per problem, the waypoints are
-//               formed on the lane (device/line.hpp), a problem stops at its first failed waypoint and line.reached counts the ones
-//               before it.  Needs a stop rule, as Solutions.
-//   Goalset:    G x K = 1 << (goal.log2G + goal.ms.log2K) candidates per problem in ONE launch, start k against goal g, the best one stored
-//               and each goal's reachability (ikgpu_dls_goalset_batch; dls_chain_goalset_body, hot_goalset_body): `io.targets` holds the G
-//               slabs of goals, B x G x K lanes.
-//   Path:       P x T chained solves per problem in ONE launch along the Cartesian path through the problem's P via poses, with the
-//               joint-step rule (ikgpu_dls_path_batch; dls_chain_path_body, hot_path_body): `io.targets` holds the P slabs of vias, the
-//               waypoints are formed on the lane (device/line.hpp), a problem stops at its first waypoint that was not met and
-//               path.reached counts the ones before it.  Needs a stop rule, as Line.
+//               stop rule: the never-stop visitor converges nowhere.
+//   Line:       T chained solves per problem along the straight line from the pose at q0 to the problem's goal (ikgpu_dls_line_batch;
+//               dls_chain_line_body, hot_line_body): `io.targets` holds ONE goal per problem, the waypoints are formed on the lane
+//               (device/line.hpp), a problem stops at its first failed waypoint and line.reached counts the ones before it.  Needs a
+//               stop rule: nothing is ever reached without one.
+//   Goalset:    G x K = 1 << (goal.log2G + goal.ms.log2K) candidates per problem, start k against goal g, the best one stored and each
+//               goal's reachability (ikgpu_dls_goalset_batch; dls_chain_goalset_body, hot_goalset_body): `io.targets` holds the G slabs of
+//               goals, B x G x K lanes, problem gid / (G K) with goal (gid / K) % G and start gid % K.
+//   Path:       P x T chained solves per problem along the Cartesian path through the problem's P via poses, with the joint-step rule
+//               (ikgpu_dls_path_batch; dls_chain_path_body, hot_path_body): `io.targets` holds the P slabs of vias, the waypoints are
+//               formed on the lane (device/line.hpp), a problem stops at its first waypoint that was not met and path.reached counts
+//               the ones before it.  Needs a stop rule, as Line.
 //   Pick:       the Multistart lanes (pick.ms), the start that met the stop rule with the smallest cost stored (ikgpu_dls_pick_batch;
-//               dls_chain_pick_body, hot_pick_body).  Needs a stop rule, as Solutions.
+//               dls_chain_pick_body, hot_pick_body), one kernel for the four cost rules.  Needs a stop rule, as Solutions.
 //   PathMultistart: the Multistart lanes (pms.ms) against via 0 = `io.targets`' slab 0, every start that entered then SCOUTS the path
 //               through the pms.P slabs behind it without storing a trajectory, and the start that gets furthest is stored with its
 //               count (ikgpu_dls_path_multistart_batch; dls_chain_path_multistart_body, hot_path_multistart_body).  Needs a stop rule.
-// Track, Multistart, Solutions, Line, Goalset, Path, Pick and PathMultistart are always lock-step: no LDS, no queue slot, no worklist, no allocation, so the launch is
-// capturable.
+// X(job, Tail = the type of the tail argument, its member of ChainJob, the body of `int lane_shift(const Tail &j)` = log2 of the lanes a
+// problem takes, whether the job has a never-stop form)
+#define IKGPU_CHAIN_JOBS(X)                                                                 \
+    X(Track,          int,                       T,    0,                    true)          \
+    X(Multistart,     ikdev::MultistartArgs,     ms,   j.log2K,              true)          \
+    X(Solutions,      ikdev::SolutionsArgs,      sol,  j.ms.log2K,           false)         \
+    X(Line,           ikdev::LineArgs,           line, 0,                    false)         \
+    X(Goalset,        ikdev::GoalsetArgs,        goal, j.log2G + j.ms.log2K, true)          \
+    X(Path,           ikdev::PathArgs,           path, 0,                    false)         \
+    X(Pick,           ikdev::PickArgs,           pick, j.ms.log2K,           false)         \
+    X(PathMultistart, ikdev::PathMultistartArgs, pms,  j.ms.log2K,           false)
+
 struct ChainJob {
-    enum Kind { Solve, Track, Multistart, Solutions, Line, Goalset, Path, Pick, PathMultistart } kind = Solve;
-    int T = 0;                     // Track: the number of waypoints
-    ikdev::MultistartArgs ms{};    // Multistart
-    ikdev::SolutionsArgs sol{};    // Solutions
-    ikdev::LineArgs line{};        // Line
-    ikdev::GoalsetArgs goal{};     // Goalset
-    ikdev::PathArgs path{};        // Path
-    ikdev::PickArgs pick{};        // Pick
-    ikdev::PathMultistartArgs pms{};   // PathMultistart
-    int64_t lanes(int64_t B) const {   // one lane per problem, per start, or per (goal, start)
-        return kind == Multistart ? B << ms.log2K : kind == Solutions ? B << sol.ms.log2K : kind == Goalset ? B << (goal.log2G + goal.ms.log2K) : kind == Pick ? B << pick.ms.log2K
-               : kind == PathMultistart ? B << pms.ms.log2K : B;
-    }
+#define X(NAME, TAIL, MEMBER, SHIFT, NEVER) , NAME
+    enum Kind { Solve IKGPU_CHAIN_JOBS(X) } kind = Solve;
+#undef X
+#define X(NAME, TAIL, MEMBER, SHIFT, NEVER) TAIL MEMBER{};
+    IKGPU_CHAIN_JOBS(X)
+#undef X
+    inline int64_t lanes(int64_t B) const;   // one lane per problem, per start, or per (goal, start)
 };
+
+// A row of IKGPU_CHAIN_JOBS as a type: what with_chain_job hands a launcher.
+template <ChainJob::Kind K>
+struct ChainJobRule;
+#define X(NAME, TAIL, MEMBER, SHIFT, NEVER)                                                                         \
+    template <>                                                                                                     \
+    struct ChainJobRule<ChainJob::NAME> {                                                                           \
+        static constexpr ChainJob::Kind kind = ChainJob::NAME;                                                      \
+        static constexpr bool never_stop_form = NEVER;                                                              \
+        using Tail = TAIL;                                                                                          \
+        static const Tail &tail(const ChainJob &job) { return job.MEMBER; }                                         \
+        static int lane_shift(const Tail &j) { (void)j; return SHIFT; }                                             \
+    };
+IKGPU_CHAIN_JOBS(X)
+#undef X
+
+// The lock-step job `job` as its rule: f(ChainJobRule<kind>{}, std::bool_constant<never_stop>{}) -- the only place that turns
+// job.kind into a type, and the only place that refuses a job without a never-stop form when the call has no stop rule
+// (hipErrorInvalidValue, f not called and not instantiated for that form: nothing is launched).  Solve is not a lock-step job; its
+// launchers take run_stop_rule before they come here.
+template <class Rule, class F>
+inline hipError_t with_chain_job_form(bool never_stop, F f) {
+    if (!never_stop) return f(Rule{}, std::false_type{});
+    if constexpr (Rule::never_stop_form) return f(Rule{}, std::true_type{});
+    else return hipErrorInvalidValue;
+}
+template <class F>
+inline hipError_t with_chain_job(const ChainJob &job, bool never_stop, F f) {
+    switch (job.kind) {
+#define X(NAME, TAIL, MEMBER, SHIFT, NEVER) \
+    case ChainJob::NAME: return with_chain_job_form<ChainJobRule<ChainJob::NAME>>(never_stop, f);
+        IKGPU_CHAIN_JOBS(X)
+#undef X
+    case ChainJob::Solve: break;
+    }
+    return hipErrorInvalidValue;
+}
+inline int64_t ChainJob::lanes(int64_t B) const {
+    int shift = 0;
+    (void)with_chain_job(*this, false, [&](auto rule, auto) { shift = decltype(rule)::lane_shift(decltype(rule)::tail(*this)); return hipSuccess; });
+    return B << shift;
+}
 
 // Returns hipSuccess or the launch error. Throws std::runtime_error for an un-instantiated shape.
 hipError_t launch_dls_chain(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job,

@@ -42,65 +42,22 @@ __global__ __launch_bounds__(kBlock, IKGPU_HOT_REFILL_WAVES) void dls_chain_hot_
     ikdev::hot_refill_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, queue, chunk);
 }
 
-// T chained solves per problem in one launch, q in registers between them (device/chain_hot.hpp hot_track_body; include/ikgpu.h
-// ikgpu_dls_track_batch).  Always lock-step per waypoint; no queue slot, no worklist, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_track_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const int T) {
-    ikdev::hot_track_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, T);
-}
-
-// K starts per problem in one launch, the best one stored (device/chain_hot.hpp hot_multistart_body; include/ikgpu.h
-// ikgpu_dls_multistart_batch): lane gid serves problem gid / K with start gid % K.  Lock-step; no LDS beyond the sin / cos table, no queue slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_multistart_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::MultistartArgs ms) {
-    ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms);
-}
-
-// K starts per problem in one launch, the converged one with the smallest cost stored (device/chain_hot.hpp hot_pick_body; include/ikgpu.h
-// ikgpu_dls_pick_batch): the multi-start kernel's lane mapping, one instantiation for the four rules.  Stop rule only; lock-step; no LDS
-// beyond the sin / cos table, no queue slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_pick_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::PickArgs pk) {
-    ikdev::hot_pick_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pk);
-}
-
-// K starts per problem in one launch against via 0, each scouting the path behind it without a trajectory store, the one that gets
-// furthest stored (device/chain_hot.hpp hot_path_multistart_body; include/ikgpu.h ikgpu_dls_path_multistart_batch): the multi-start
-// kernel's lane mapping.  Stop rule only; lock-step per solve; no LDS beyond the sin / cos table, no queue slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_path_multistart_kernel(const ChainKernelArgs<NJ> a, const HotTable t,
-                                                                               const ikdev::PathMultistartArgs pm) {
-    ikdev::hot_path_multistart_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pm);
-}
-
-// G goals and K starts per problem in one launch, the best candidate stored (device/chain_hot.hpp hot_goalset_body; include/ikgpu.h
-// ikgpu_dls_goalset_batch): lane gid serves problem gid / (G K) with goal (gid / K) % G and start gid % K.  Lock-step; no LDS, no queue
-// slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_goalset_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::GoalsetArgs ga) {
-    ikdev::hot_goalset_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ga);
-}
-
-// K starts per problem in one launch, the distinct converged ones stored (device/chain_hot.hpp hot_solutions_body; include/ikgpu.h
-// ikgpu_dls_solutions_batch): the multi-start kernel's lane mapping.  Stop rule only; lock-step; no LDS beyond the sin / cos table, no queue slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_solutions_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::SolutionsArgs sa) {
-    ikdev::hot_solutions_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, sa);
-}
-
-// A straight Cartesian line to one goal per problem in one launch (device/chain_hot.hpp hot_line_body; include/ikgpu.h
-// ikgpu_dls_line_batch).  Stop rule only; lock-step per waypoint; no LDS beyond the sin / cos table, no queue slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_line_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::LineArgs la) {
-    ikdev::hot_line_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, la);
-}
-
-// A Cartesian path through P vias per problem with the joint-step rule in one launch (device/chain_hot.hpp hot_path_body; include/ikgpu.h
-// ikgpu_dls_path_batch).  Stop rule only; lock-step per waypoint; no LDS beyond the sin / cos table, no queue slot, no allocation.
-template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
-__global__ __launch_bounds__(kBlock) void dls_chain_hot_path_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const ikdev::PathArgs pa) {
-    ikdev::hot_path_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pa);
-}
+// The lock-step jobs of kernels.hpp IKGPU_CHAIN_JOBS on the hot program, one overload per tail argument: the job's entry of
+// device/chain_hot.hpp, on the never-stop visitor's own instantiation where the job has one (with_chain_job asks for no other).
+#define IKGPU_HOT_JOB_KERNEL(TAIL)                                               \
+    template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2, bool NEVERSTOP> \
+    __global__ __launch_bounds__(kBlock) void dls_chain_hot_job_kernel(const ChainKernelArgs<NJ> a, const HotTable t, const TAIL)
+IKGPU_HOT_JOB_KERNEL(int T) { ikdev::hot_track_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, T); }
+IKGPU_HOT_JOB_KERNEL(ikdev::MultistartArgs ms) { ikdev::hot_multistart_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ms); }
+IKGPU_HOT_JOB_KERNEL(ikdev::GoalsetArgs ga) { ikdev::hot_goalset_entry<NJ, ChainStruct<C0, C1, C2>, NEVERSTOP>(a, t, ga); }
+#define IKGPU_HOT_STOP_RULE_ONLY static_assert(!NEVERSTOP, "a job that needs a stop rule has no never-stop kernel");
+IKGPU_HOT_JOB_KERNEL(ikdev::SolutionsArgs sa) { IKGPU_HOT_STOP_RULE_ONLY ikdev::hot_solutions_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, sa); }
+IKGPU_HOT_JOB_KERNEL(ikdev::LineArgs la) { IKGPU_HOT_STOP_RULE_ONLY ikdev::hot_line_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, la); }
+IKGPU_HOT_JOB_KERNEL(ikdev::PathArgs pa) { IKGPU_HOT_STOP_RULE_ONLY ikdev::hot_path_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pa); }
+IKGPU_HOT_JOB_KERNEL(ikdev::PickArgs pk) { IKGPU_HOT_STOP_RULE_ONLY ikdev::hot_pick_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pk); }
+IKGPU_HOT_JOB_KERNEL(ikdev::PathMultistartArgs pm) { IKGPU_HOT_STOP_RULE_ONLY ikdev::hot_path_multistart_entry<NJ, ChainStruct<C0, C1, C2>>(a, t, pm); }
+#undef IKGPU_HOT_STOP_RULE_ONLY
+#undef IKGPU_HOT_JOB_KERNEL
 
 // X(NJ, code0, code1, code2)
 #define IKGPU_HOT_SHAPES(X)                                                                                                   \
@@ -145,7 +102,8 @@ std::string chain_kernel_name(const ProblemHost &ph) {
 
 namespace {
 
-// One pre-built shape: the kernel the job asks for, on the never-stop visitor's own instantiation when the call has no stop rule.
+// One pre-built shape: the kernel the job asks for, on the never-stop visitor's own instantiation when the call has no stop rule
+// (solve: the lambda; every other job: with_chain_job, which refuses a never-stop call of a job without that form).
 template <int NJ, uint64_t C0, uint64_t C1, uint64_t C2>
 hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
                             hipStream_t stream, const HotTable &t) {
@@ -155,29 +113,9 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
     const dim3 grid(static_cast<unsigned>((job.lanes(io.B) + kBlock - 1) / kBlock)), block(kBlock);
     auto launch = [&](auto never) -> hipError_t {
         constexpr bool NEVER = decltype(never)::value;
-        if (job.kind == ChainJob::Track) {
-            hipLaunchKernelGGL((dls_chain_hot_track_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.T);
-        } else if (job.kind == ChainJob::Multistart) {
-            hipLaunchKernelGGL((dls_chain_hot_multistart_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.ms);
-        } else if (job.kind == ChainJob::Goalset) {
-            hipLaunchKernelGGL((dls_chain_hot_goalset_kernel<NJ, C0, C1, C2, NEVER>), grid, block, 0, stream, a, t, job.goal);
-        } else if (job.kind == ChainJob::Solutions) {
-            if constexpr (NEVER) return hipErrorInvalidValue;   // (no start converges without a stop rule: the entry point refuses the call)
-            else hipLaunchKernelGGL((dls_chain_hot_solutions_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.sol);
-        } else if (job.kind == ChainJob::Pick) {
-            if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
-            else hipLaunchKernelGGL((dls_chain_hot_pick_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.pick);
-        } else if (job.kind == ChainJob::PathMultistart) {
-            if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
-            else hipLaunchKernelGGL((dls_chain_hot_path_multistart_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.pms);
-        } else if (job.kind == ChainJob::Line) {
-            if constexpr (NEVER) return hipErrorInvalidValue;   // (nothing is ever reached without a stop rule: refused likewise)
-            else hipLaunchKernelGGL((dls_chain_hot_line_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.line);
-        } else if (job.kind == ChainJob::Path) {
-            if constexpr (NEVER) return hipErrorInvalidValue;   // (likewise)
-            else hipLaunchKernelGGL((dls_chain_hot_path_kernel<NJ, C0, C1, C2>), grid, block, 0, stream, a, t, job.path);
-        } else if constexpr (NEVER) {
+        if constexpr (NEVER) {
             hipLaunchKernelGGL((dls_chain_hot_kernel<NJ, C0, C1, C2, true>), grid, block, 0, stream, a, t);
+            return hipGetLastError();
         } else {
             const int64_t rgrid = refill_grid(reinterpret_cast<const void *>(dls_chain_hot_refill_kernel<NJ, C0, C1, C2>), io.B);
             return run_stop_rule(dt.queues, io, prm, stream, a, false, rgrid, PassThrough{&ph, &dt}, [&] {
@@ -188,9 +126,14 @@ hipError_t launch_hot_shape(const ProblemHost &ph, const DeviceTables &dt, const
                 return hipGetLastError();
             });
         }
-        return hipGetLastError();
     };
-    return prm.stop_sq_tol < 0.0 ? launch(std::true_type{}) : launch(std::false_type{});
+    const bool never_stop = prm.stop_sq_tol < 0.0;
+    if (job.kind == ChainJob::Solve) return never_stop ? launch(std::true_type{}) : launch(std::false_type{});
+    return with_chain_job(job, never_stop, [&](auto rule, auto never) -> hipError_t {
+        // (the overload of dls_chain_hot_job_kernel that takes the job's tail)
+        hipLaunchKernelGGL((dls_chain_hot_job_kernel<NJ, C0, C1, C2, decltype(never)::value>), grid, block, 0, stream, a, t, decltype(rule)::tail(job));
+        return hipGetLastError();
+    });
 }
 
 }  // namespace

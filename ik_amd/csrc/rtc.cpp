@@ -125,53 +125,38 @@ uint64_t fnv1a(uint64_t h, const void *data, size_t n) {
 const char *const kFlags[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-fast-math", "-ffp-contract=on",
                               "-fno-signed-zeros", "-fno-honor-nans", "-fno-honor-infinities"};
 
-// The entry points of a run-time compiled hot module, one row each, in the order of the generated source: hot_source writes the
-// row's wrapper, module_for loads it into HotModule::fn[row], launch_shape launches fn[hot_entry(kind, never-stop)] or the refill row.
-//   extern "C" __global__ <bounds> void <name>(const ikdev::ChainKernelArgs<NJ> a, const ikdev::HotTable t<params>) {
-//       ikdev::<entry><NJ, S<flag>>(a, t<args>);
+// The entry points of a run-time compiled hot module, one row per chain job (kernels.hpp IKGPU_CHAIN_JOBS) in the order of the
+// generated source.  hot_source writes a row's wrappers, module_for loads them into HotModule::fn[row], launch_shape launches them:
+//   extern "C" __global__ <bounds> void <name>_never | <name>_stop(const ikdev::ChainKernelArgs<NJ> a, const ikdev::HotTable t<params>) {
+//       ikdev::<entry><NJ, S[, true | false]>(a, t<args>);
 //   }
-enum { kHotNever, kHotStop, kHotRefill, kHotTrackNever, kHotTrackStop, kHotMultistartNever, kHotMultistartStop, kHotSolutionsStop, kHotLineStop,
-       kHotGoalsetNever, kHotGoalsetStop, kHotPathStop, kHotPickStop, kHotPathMultistartStop, kHotEntries };
-struct HotEntry {
-    const char *name, *params, *entry, *flag, *args;
-    bool refill_bounds;   // the refill kernel's launch bounds (hot_source) instead of one wave per SIMD
+// <name>_never and the flag only for a job with a never-stop form.  The solve's row is followed by its refill twin, ikgpu_hot_refill.
+struct HotRow {
+    ChainJob::Kind kind;
+    bool never_stop_form;
+    const char *name, *params, *entry, *args;
 };
-const HotEntry kHotEntryTable[kHotEntries] = {
-    {"ikgpu_hot_never", "", "hot_kernel_entry", ", true", "", false},
-    {"ikgpu_hot_stop", "", "hot_kernel_entry", ", false", "", false},
-    {"ikgpu_hot_refill", ", unsigned long long *queue, int chunk", "hot_refill_entry", "", ", queue, chunk", true},
-    // T chained solves in one launch (ikgpu_dls_track_batch)
-    {"ikgpu_hot_track_never", ", const int T", "hot_track_entry", ", true", ", T", false},
-    {"ikgpu_hot_track_stop", ", const int T", "hot_track_entry", ", false", ", T", false},
-    // K starts per problem in one launch, the best one stored (ikgpu_dls_multistart_batch)
-    {"ikgpu_hot_multistart_never", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", true", ", ms", false},
-    {"ikgpu_hot_multistart_stop", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", false", ", ms", false},
-    // ... the distinct converged ones stored (ikgpu_dls_solutions_batch): a stop rule always, so one entry
-    {"ikgpu_hot_solutions_stop", ", const ikdev::SolutionsArgs sa", "hot_solutions_entry", "", ", sa", false},
-    // a straight Cartesian line to one goal per problem (ikgpu_dls_line_batch): a stop rule always, so one entry
-    {"ikgpu_hot_line_stop", ", const ikdev::LineArgs la", "hot_line_entry", "", ", la", false},
-    // G goals and K starts per problem in one launch, the best candidate stored (ikgpu_dls_goalset_batch)
-    {"ikgpu_hot_goalset_never", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", true", ", ga", false},
-    {"ikgpu_hot_goalset_stop", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", false", ", ga", false},
-    // a Cartesian path through P vias per problem with the joint-step rule (ikgpu_dls_path_batch): a stop rule always, so one entry
-    {"ikgpu_hot_path_stop", ", const ikdev::PathArgs pa", "hot_path_entry", "", ", pa", false},
-    // K starts per problem in one launch, the converged one with the smallest cost stored (ikgpu_dls_pick_batch): a stop rule always, so one entry
-    {"ikgpu_hot_pick_stop", ", const ikdev::PickArgs pk", "hot_pick_entry", "", ", pk", false},
-    // K starts per problem against via 0, each scouting the path behind it, the one that gets furthest stored
-    // (ikgpu_dls_path_multistart_batch): a stop rule always, so one entry
-    {"ikgpu_hot_path_multistart_stop", ", const ikdev::PathMultistartArgs pm", "hot_path_multistart_entry", "", ", pm", false},
+#define HOT_JOB_ROW(JOB, NAME, PARAMS, ENTRY, ARGS) {ChainJob::JOB, ChainJobRule<ChainJob::JOB>::never_stop_form, NAME, PARAMS, ENTRY, ARGS}
+constexpr HotRow kHotRows[] = {
+    {ChainJob::Solve, true, "ikgpu_hot", "", "hot_kernel_entry", ""},
+    HOT_JOB_ROW(Track, "ikgpu_hot_track", ", const int T", "hot_track_entry", ", T"),
+    HOT_JOB_ROW(Multistart, "ikgpu_hot_multistart", ", const ikdev::MultistartArgs ms", "hot_multistart_entry", ", ms"),
+    HOT_JOB_ROW(Solutions, "ikgpu_hot_solutions", ", const ikdev::SolutionsArgs sa", "hot_solutions_entry", ", sa"),
+    HOT_JOB_ROW(Line, "ikgpu_hot_line", ", const ikdev::LineArgs la", "hot_line_entry", ", la"),
+    HOT_JOB_ROW(Goalset, "ikgpu_hot_goalset", ", const ikdev::GoalsetArgs ga", "hot_goalset_entry", ", ga"),
+    HOT_JOB_ROW(Path, "ikgpu_hot_path", ", const ikdev::PathArgs pa", "hot_path_entry", ", pa"),
+    HOT_JOB_ROW(Pick, "ikgpu_hot_pick", ", const ikdev::PickArgs pk", "hot_pick_entry", ", pk"),
+    HOT_JOB_ROW(PathMultistart, "ikgpu_hot_path_multistart", ", const ikdev::PathMultistartArgs pm", "hot_path_multistart_entry", ", pm"),
 };
-// The row of a job, or -1: a solution-set, line or path job has no never-stop entry.
-int hot_entry(ChainJob::Kind kind, bool never) {
-    if (kind == ChainJob::Solutions) return never ? -1 : kHotSolutionsStop;
-    if (kind == ChainJob::Line) return never ? -1 : kHotLineStop;
-    if (kind == ChainJob::Path) return never ? -1 : kHotPathStop;
-    if (kind == ChainJob::Pick) return never ? -1 : kHotPickStop;
-    if (kind == ChainJob::PathMultistart) return never ? -1 : kHotPathMultistartStop;
-    if (kind == ChainJob::Goalset) return never ? kHotGoalsetNever : kHotGoalsetStop;
-    static const int first[] = {kHotNever, kHotTrackNever, kHotMultistartNever};   // by ChainJob::Kind; the stop-rule twin follows
-    return first[kind] + (never ? 0 : 1);
+#undef HOT_JOB_ROW
+constexpr int kHotRowCount = static_cast<int>(sizeof(kHotRows) / sizeof(kHotRows[0]));
+constexpr HotRow kHotRefill = {ChainJob::Solve, false, "ikgpu_hot_refill", ", unsigned long long *queue, int chunk", "hot_refill_entry", ", queue, chunk"};
+constexpr int hot_row(ChainJob::Kind kind) {   // the row of a job, or -1
+    for (int i = 0; i < kHotRowCount; ++i)
+        if (kHotRows[i].kind == kind) return i;
+    return -1;
 }
+inline std::string hot_name(const HotRow &row, bool never) { return std::string(row.name) + (never ? "_never" : "_stop"); }
 
 // values: non-structural placement entries of the chain.  The refill kernel asks for two waves per SIMD (256 registers) unless the
 // parked table alone would take most of them.  The on-disk cache key hashes this text: one changed byte recompiles every chain that
@@ -185,10 +170,15 @@ std::string hot_source(int nj, const uint64_t code[3], int values, int prismatic
                   static_cast<unsigned long long>(code[0]), static_cast<unsigned long long>(code[1]), static_cast<unsigned long long>(code[2]), pm);
     const std::string n = std::to_string(nj);
     std::string src = head;
-    for (const HotEntry &e : kHotEntryTable)
-        src += std::string("extern \"C\" __global__ ") + (e.refill_bounds && values <= 40 ? "__launch_bounds__(64, 2)" : "__launch_bounds__(64)") +
-               " void " + e.name + "(const ikdev::ChainKernelArgs<" + n + "> a, const ikdev::HotTable t" + e.params + ") {\n    ikdev::" +
-               e.entry + "<" + n + ", S" + e.flag + ">(a, t" + e.args + ");\n}\n";
+    auto wrapper = [&](const HotRow &row, const std::string &name, const char *bounds, const char *flag) {
+        src += std::string("extern \"C\" __global__ ") + bounds + " void " + name + "(const ikdev::ChainKernelArgs<" + n + "> a, const ikdev::HotTable t" +
+               row.params + ") {\n    ikdev::" + row.entry + "<" + n + ", S" + flag + ">(a, t" + row.args + ");\n}\n";
+    };
+    for (const HotRow &row : kHotRows) {
+        if (row.never_stop_form) wrapper(row, hot_name(row, true), "__launch_bounds__(64)", ", true");
+        wrapper(row, hot_name(row, false), "__launch_bounds__(64)", row.never_stop_form ? ", false" : "");
+        if (row.kind == ChainJob::Solve) wrapper(kHotRefill, kHotRefill.name, values <= 40 ? "__launch_bounds__(64, 2)" : "__launch_bounds__(64)", "");
+    }
     return src;
 }
 
@@ -271,7 +261,8 @@ struct HotCode {
 };
 struct HotModule {
     hipModule_t mod = nullptr;
-    hipFunction_t fn[kHotEntries] = {};   // by row of kHotEntryTable
+    hipFunction_t fn[kHotRowCount][2] = {};   // by row of kHotRows: [0] the stop-rule form, [1] the never-stop form where the job has one
+    hipFunction_t refill = nullptr;
     int refill_waves_per_cu = 0;
 };
 
@@ -556,10 +547,13 @@ bool module_for(const ProblemHost &ph, HotModule &out, hipError_t *err) {
     HotModule &m = g_modules[mkey];
     if (!m.mod) {
         hipError_t e = hipModuleLoadData(&m.mod, hc.code.data());
-        for (int i = 0; i < kHotEntries && e == hipSuccess; ++i) e = hipModuleGetFunction(&m.fn[i], m.mod, kHotEntryTable[i].name);
+        for (int i = 0; i < kHotRowCount; ++i)
+            for (int never = 0; never <= (kHotRows[i].never_stop_form ? 1 : 0) && e == hipSuccess; ++never)
+                e = hipModuleGetFunction(&m.fn[i][never], m.mod, hot_name(kHotRows[i], never != 0).c_str());
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.refill, m.mod, kHotRefill.name);
         if (e == hipSuccess) {
             int per_cu = 0;
-            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.fn[kHotRefill], 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.refill, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
             m.refill_waves_per_cu = per_cu;
         }
         if (e != hipSuccess) { *err = e; m = HotModule{}; return false; }
@@ -579,100 +573,63 @@ int64_t module_refill_waves(int waves_per_cu, int64_t B) {
 }
 
 // A launch of one of the module's kernels on the kernel-argument segment they share: (ChainKernelArgs<NJ> a, HotTable t), then what the
-// job's kernel takes after them -- nothing, (queue, chunk) for the refill kernel, T, or the multi-start arguments -- at natural
-// alignment.  Each kernel is handed exactly the bytes of its own parameters.
+// job's kernel takes after them at natural alignment -- nothing for the solve, (queue, chunk) for its refill twin, the job's tail
+// argument (kernels.hpp IKGPU_CHAIN_JOBS) for every other.  Each kernel is handed exactly the bytes of its own parameters: the head,
+// and for a kernel with a tail the head + sizeof(Tail); the refill kernel's segment ends with its last parameter, the int `chunk`.
+struct HotRefillTail {
+    unsigned long long *queue;
+    int chunk;
+};
+template <class Tail> constexpr size_t kHotTailBytes = sizeof(Tail);
+template <> constexpr size_t kHotTailBytes<HotRefillTail> = offsetof(HotRefillTail, chunk) + sizeof(int);
+template <int NJ, class Tail>
+struct HotArgs {
+    ikdev::ChainKernelArgs<NJ> a;
+    ikdev::HotTable t;
+    Tail tail;
+    hipError_t fill(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ikgpu_dls_params &prm) {
+        fill_chain_kernel_args(a, ph, dt);
+        fill_solve_args(a, io, prm);
+        if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
+        std::memcpy(t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
+        return hipSuccess;
+    }
+    // the first `with_tail ? head + tail : head` bytes of the segment to `fn`
+    hipError_t launch(hipFunction_t fn, int64_t grid, bool with_tail, hipStream_t stream) {
+        constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
+        static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && offsetof(HotArgs, tail) == kHead &&
+                          sizeof(HotArgs) >= kHead + kHotTailBytes<Tail>,
+                      "argument layout: the tail follows (a, t) without padding, as the kernel's own parameters do");
+        size_t nbytes = with_tail ? kHead + kHotTailBytes<Tail> : kHead;
+        void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, this, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
+        return hipModuleLaunchKernel(fn, static_cast<unsigned>(grid), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
+    }
+};
+
 template <int NJ>
 hipError_t launch_shape(const ProblemHost &ph, const DeviceTables &dt, const BatchIO &io, const ChainJob &job, const ikgpu_dls_params &prm,
                         hipStream_t stream, const HotModule &m) {
-    struct Args {
-        ikdev::ChainKernelArgs<NJ> a;
-        ikdev::HotTable t;
-        union {
-            struct { unsigned long long *queue; int chunk; } refill;
-            int T;
-            ikdev::MultistartArgs ms;
-            ikdev::SolutionsArgs sa;
-            ikdev::LineArgs la;
-            ikdev::GoalsetArgs ga;
-            ikdev::PathArgs pa;
-            ikdev::PickArgs pk;
-            ikdev::PathMultistartArgs pm;
-        } tail;
-    } args{};
-    constexpr size_t kHead = sizeof(ikdev::ChainKernelArgs<NJ>) + sizeof(ikdev::HotTable);
-    static_assert(sizeof(ikdev::ChainKernelArgs<NJ>) % 8 == 0 && sizeof(ikdev::HotTable) % 8 == 0 && alignof(ikdev::MultistartArgs) == 8 &&
-                      alignof(ikdev::SolutionsArgs) == 8 && alignof(ikdev::LineArgs) == 8 && alignof(ikdev::GoalsetArgs) == 8 &&
-                      alignof(ikdev::PathArgs) == 8 && alignof(ikdev::PickArgs) == 8 && alignof(ikdev::PathMultistartArgs) == 8,
-                  "argument layout");
-    constexpr size_t kBytesPlain = offsetof(Args, tail), kBytesRefill = offsetof(Args, tail.refill.chunk) + sizeof(int),
-                     kBytesTrack = offsetof(Args, tail.T) + sizeof(int),
-                     kBytesMultistart = offsetof(Args, tail) + sizeof(ikdev::MultistartArgs), kBytesSolutions = offsetof(Args, tail) + sizeof(ikdev::SolutionsArgs),
-                     kBytesLine = offsetof(Args, tail) + sizeof(ikdev::LineArgs), kBytesGoalset = offsetof(Args, tail) + sizeof(ikdev::GoalsetArgs),
-                     kBytesPath = offsetof(Args, tail) + sizeof(ikdev::PathArgs), kBytesPick = offsetof(Args, tail) + sizeof(ikdev::PickArgs),
-                     kBytesPathMultistart = offsetof(Args, tail) + sizeof(ikdev::PathMultistartArgs);
-    static_assert(kBytesPlain == kHead, "never / stop: (a, t)");
-    static_assert(kBytesRefill == kHead + sizeof(unsigned long long *) + sizeof(int), "refill: (a, t, queue, chunk), through chunk");
-    static_assert(kBytesTrack == kHead + sizeof(int), "track: (a, t, T), through T");
-    static_assert(kBytesMultistart == kHead + sizeof(ikdev::MultistartArgs), "multi-start: the whole of (a, t, ms)");
-    static_assert(kBytesSolutions == kHead + sizeof(ikdev::SolutionsArgs), "solution set: the whole of (a, t, sa)");
-    static_assert(kBytesLine == kHead + sizeof(ikdev::LineArgs), "line: the whole of (a, t, la)");
-    static_assert(kBytesGoalset == kHead + sizeof(ikdev::GoalsetArgs), "goal set: the whole of (a, t, ga)");
-    static_assert(kBytesPath == kHead + sizeof(ikdev::PathArgs), "path: the whole of (a, t, pa)");
-    static_assert(kBytesPick == kHead + sizeof(ikdev::PickArgs), "pick: the whole of (a, t, pk)");
-    static_assert(kBytesPathMultistart == kHead + sizeof(ikdev::PathMultistartArgs), "path multi-start: the whole of (a, t, pm)");
-    ikdev::ChainKernelArgs<NJ> &a = args.a;
-    fill_chain_kernel_args(a, ph, dt);
-    fill_solve_args(a, io, prm);
-    if (ph.chain_hot.size() > static_cast<size_t>(ikdev::kHotTableMax)) return hipErrorInvalidValue;
-    std::memcpy(args.t.v, ph.chain_hot.data(), ph.chain_hot.size() * sizeof(double));
-
     const int64_t waves = (job.lanes(io.B) + 63) / 64;
-    auto launch = [&](int entry, int64_t grid, size_t nbytes) {
-        void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
-        return hipModuleLaunchKernel(m.fn[entry], static_cast<unsigned>(grid), 1, 1, 64, 1, 1, 0, stream, nullptr, config);
-    };
-    const bool never = prm.stop_sq_tol < 0.0;
-    const int entry = hot_entry(job.kind, never);
-    if (entry < 0) return hipErrorInvalidValue;
-    if (job.kind == ChainJob::Solutions) {
-        args.tail.sa = job.sol;
-        return launch(entry, waves, kBytesSolutions);
-    }
-    if (job.kind == ChainJob::Line) {
-        args.tail.la = job.line;
-        return launch(entry, waves, kBytesLine);
-    }
-    if (job.kind == ChainJob::Path) {
-        args.tail.pa = job.path;
-        return launch(entry, waves, kBytesPath);
-    }
-    if (job.kind == ChainJob::Pick) {
-        args.tail.pk = job.pick;
-        return launch(entry, waves, kBytesPick);
-    }
-    if (job.kind == ChainJob::PathMultistart) {
-        args.tail.pm = job.pms;
-        return launch(entry, waves, kBytesPathMultistart);
-    }
-    if (job.kind == ChainJob::Goalset) {
-        args.tail.ga = job.goal;
-        return launch(entry, waves, kBytesGoalset);
-    }
-    if (job.kind == ChainJob::Track) {
-        args.tail.T = job.T;
-        return launch(entry, waves, kBytesTrack);
-    }
-    if (job.kind == ChainJob::Multistart) {
-        args.tail.ms = job.ms;
-        return launch(entry, waves, kBytesMultistart);
-    }
-    if (never) return launch(entry, waves, kBytesPlain);
+    const bool never_stop = prm.stop_sq_tol < 0.0;
+    if (job.kind != ChainJob::Solve)
+        return with_chain_job(job, never_stop, [&](auto rule, auto never) -> hipError_t {
+            using Rule = decltype(rule);
+            static_assert(hot_row(Rule::kind) >= 0, "every chain job has a row of kHotRows");
+            HotArgs<NJ, typename Rule::Tail> args{};
+            if (const hipError_t e = args.fill(ph, dt, io, prm); e != hipSuccess) return e;
+            args.tail = Rule::tail(job);
+            return args.launch(m.fn[hot_row(Rule::kind)][decltype(never)::value ? 1 : 0], waves, true, stream);
+        });
+    HotArgs<NJ, HotRefillTail> args{};
+    if (const hipError_t e = args.fill(ph, dt, io, prm); e != hipSuccess) return e;
+    constexpr int kSolve = hot_row(ChainJob::Solve);
+    if (never_stop) return args.launch(m.fn[kSolve][1], waves, false, stream);
     const int64_t resident = module_refill_waves(m.refill_waves_per_cu, io.B);
-    return run_stop_rule(dt.queues, io, prm, stream, a, false, resident, PassThrough{&ph, &dt}, [&] { return launch(entry, waves, kBytesPlain); },
+    return run_stop_rule(dt.queues, io, prm, stream, args.a, false, resident, PassThrough{&ph, &dt},
+                         [&] { return args.launch(m.fn[kSolve][0], waves, false, stream); },
                          [&](unsigned long long *queue, int chunk) {
-                             args.tail.refill.queue = queue;
-                             args.tail.refill.chunk = chunk;
-                             return launch(kHotRefill, resident, kBytesRefill);
+                             args.tail = HotRefillTail{queue, chunk};
+                             return args.launch(m.refill, resident, true, stream);
                          });
 }
 

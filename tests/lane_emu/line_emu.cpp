@@ -54,7 +54,7 @@ ikdev::ChainDesc<NJ> desc_of(const ikgpu::ProblemHost &ph) {
     return d;
 }
 
-// the waypoints alone: what the kernel behind ikgpu_line_targets does for a chain problem (kernels.hip line_targets_chain_kernel)
+// the waypoints alone: what the kernel behind ikgpu_line_targets does for a chain problem (kernels.hip path_targets_chain_kernel with P = 1)
 template <int NJ>
 void run_waypoints(const ikgpu::ProblemHost &ph, const IO &io) {
     const ikdev::ChainDesc<NJ> d = desc_of<NJ>(ph);

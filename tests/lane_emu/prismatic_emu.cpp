@@ -308,7 +308,7 @@ int prismatic_emu_track(const char *urdf, size_t len, const ikgpu_task *task, in
     });
 }
 
-// goals [12 x B]; q_traj null: the waypoints alone into waypoints [T][12 x B] (kernels.hip line_targets_chain_kernel); else
+// goals [12 x B]; q_traj null: the waypoints alone into waypoints [T][12 x B] (kernels.hip path_targets_chain_kernel with P = 1); else
 // ikgpu_dls_line_batch's outputs and visited [B], the waypoints the lane's loop went through (line_emu.cpp)
 int prismatic_emu_line(const char *urdf, size_t len, const ikgpu_task *task, int program, int64_t B, int T, const double *q0, const double *goals,
                        const ikgpu_dls_params *prm, double *q_traj, uint8_t *success, int32_t *iters, int32_t *reached, int32_t *visited,

@@ -183,7 +183,7 @@ def _chained_oracle(O, x, W, near, ext=None):
 
 @pytest.mark.parametrize("c", CS.CASES, ids=CS.case_id)
 def test_line_job_of_every_chain_shape_on_the_device(torch_cuda, c):
-    """The line job (dls_chain_line_kernel<NJ, KT, SMASK>, and the entry ikgpu_hot_line_stop of the run-time compiled module at
+    """The line job (dls_chain_job_kernel<NJ, KT, SMASK>(a, LineArgs), and the entry ikgpu_hot_line_stop of the run-time compiled module at
     NJ = 1 .. 7) on every build of every case: CS.LINE_T waypoints towards CS.line_goals in the case's reference frame under the default
     stop rule.  Per build: the kernel's name; line_targets against oracle/twin.py with the case's reference at line_common.WAYPOINT_BAR,
     both layouts giving the same bits and the last waypoint the goal's; dls_line_batch into sentinel-filled outputs np.array_equal to

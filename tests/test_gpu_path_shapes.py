@@ -1,6 +1,6 @@
 """The path job on every chain shape of tests/chain_shapes_common.py: lengths 1 .. 8 x Position / Orientation / Full on the general build,
 unit and non-unit weights, a world-fixed oblique reference frame, and the run-time specialised hot build at lengths 1 .. 7
-(dls_chain_path_kernel<NJ, KT, SMASK>, and the entry ikgpu_hot_path_stop of the run-time compiled module) -- as
+(dls_chain_job_kernel<NJ, KT, SMASK>(a, PathArgs), and the entry ikgpu_hot_path_stop of the run-time compiled module) -- as
 tests/test_gpu_chain_shapes.py runs the line job.  B = 65 (a wave and one lane), P = 2, T = 3: via 0 is the case's own target (a near
 line from the pose at q0), via 1 the case's line goal (every third one far: paths that leave the workspace or the limits, or get there
 through a jump), in the case's reference frame.

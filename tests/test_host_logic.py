@@ -382,6 +382,40 @@ def test_chain_build_switches_and_precompile(ik, tmp_path, monkeypatch):
     assert ik.precompile(weighted) == "dls_chain<NJ=7,full,general>"
 
 
+def test_the_generated_hot_source_is_the_text_deployed_caches_were_keyed_by(ik, tmp_path, monkeypatch):
+    """The source rtc.cpp generates for a run-time compiled hot chain, byte for byte: the on-disk cache key hashes it (with the device
+    headers and the flags), so one changed byte recompiles every chain a deployment has precompiled.  Lengths and digests were recorded
+    from a build of the commit before the entry table became one row per chain job (IKGPU_RTC_DUMP, this toolchain): arm7 `tool`, a chain
+    of revolute joints, and arm8 with j2 and j5 sliding from tests/prismatic_common.py's models, frame l7 on the default build, whose
+    typedef carries the fourth ChainStruct argument.  (Not one of that module's own default-build cases: tests/test_prismatic_chain_host.py
+    compiles each of those in this process and counts the cache files, and a program is compiled and cached once per process.)"""
+    import hashlib
+    import prismatic_common as PC
+    monkeypatch.delenv("IKGPU_CHAIN_HOT", raising=False)
+    monkeypatch.delenv("IKGPU_RTC", raising=False)
+    arm = _problem(ik, "arm7", ["tool"])[1]
+    if ik.plan(arm) != "dls_chain<NJ=7,full,hot-rtc>":
+        pytest.skip("libhiprtc not loadable here")
+    sliding = PC.Case("arm8_j2_j5", "l7", 7, 2, False, "universe", "default")
+    slider = PC.make_problem(sliding, ik.Model.from_urdf_xml(PC.robot_xml(sliding.robot)))
+    recorded = ((arm, "dls_chain<NJ=7,full,hot-rtc>", 3035, "041cfe897574e647fcefc93c1f095d29bd622ccea4fe4b33563e0995acdb0019"),
+                (slider, "dls_chain<NJ=7,full,hot-rtc>", 3037, "c4a076d0e50d9c1011d5bf946b08b003f3cce371f86d1099a67bdca945733907"))
+    for i, (problem, name, length, digest) in enumerate(recorded):
+        src_dir, cache = tmp_path / ("src%d" % i), tmp_path / ("cache%d" % i)
+        src_dir.mkdir(), cache.mkdir(mode=0o700)
+        monkeypatch.setenv("IKGPU_RTC_DUMP", str(src_dir))
+        monkeypatch.setenv("IKGPU_CACHE_DIR", str(cache))
+        assert ik.precompile(problem) == name
+        dumped = os.listdir(src_dir)
+        assert len(dumped) == 1 and dumped[0].startswith("chain_hot_") and dumped[0].endswith(".hip"), dumped
+        # the source's name is its code object's (a program this process has compiled before is not compiled, or cached, again)
+        assert os.listdir(cache) in ([], [dumped[0][:-4] + ".hsaco"])
+        text = open(os.path.join(src_dir, dumped[0]), "rb").read()
+        if (len(text), hashlib.sha256(text).hexdigest()) != (length, digest):
+            print(text.decode())
+        assert (len(text), hashlib.sha256(text).hexdigest()) == (length, digest), name
+
+
 def test_shard_rule_and_slot_layout_of_the_c_abi(ik):
     """ikgpu_shard_range / ikgpu_shard_slot_layout / ikgpu_shard_slot_bytes (what ikgpu_dls_solve_batch_sharded splits and packs by)
     against their definitions; ik_amd.distributed uses the same functions for the one-process-per-GPU path."""

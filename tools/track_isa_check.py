@@ -65,10 +65,22 @@ def loops(ins):
     return sorted(found, key=lambda f: f[2]), idx
 
 
+JOBS = {"i": "track", "MultistartArgs": "multistart", "SolutionsArgs": "solutions", "LineArgs": "line", "GoalsetArgs": "goalset", "PathArgs": "path",
+        "PickArgs": "pick", "PathMultistartArgs": "path_multistart"}
+
+
+def job_of(name):
+    """The chain job of an overload of dls_chain_job_kernel / dls_chain_hot_job_kernel, from the type of its last parameter (the job's
+    tail argument, kernels.hpp IKGPU_CHAIN_JOBS): `i` for the tracking kernel's T, else ikdev::<Job>Args.  None for every other kernel."""
+    m = re.search(r"job_kernelI.*(?:ChainKernelArgsIXT_EEE|HotTableE)(i|NS\d+_\d+(\w+Args)E)$", name)
+    return JOBS.get(m.group(2) or m.group(1)) if m else None
+
+
 def short(name):
     m = re.search(r"\d+(dls_chain\w+?kernel)ILi(\d)", name)
-    tail = "never-stop" if name.rstrip("E").endswith("ELb1EEEvN5ikdev15ChainKernelArgsIXT_EEENS2_8HotTableEi") or "ELb1EEEv" in name else "stop rule" if "ELb0EEEv" in name else ""
-    return "%s<NJ=%s> %s" % (m.group(1), m.group(2), tail) if m else name
+    tail = "never-stop" if "ELb1EEEv" in name else "stop rule" if "ELb0EEEv" in name else ""
+    kernel = m.group(1).replace("job", job_of(name)) if m and job_of(name) else m.group(1) if m else None
+    return "%s<NJ=%s> %s" % (kernel, m.group(2), tail) if m else name
 
 
 def main():
@@ -87,7 +99,7 @@ def main():
         line = "%-48s %6d instructions, v_accvgpr_* %3d, scratch_* %d" % (short(name), len(idx), total_acc, scratch)
         if inner:
             line += " | iteration loop %5d instructions, v_accvgpr_* inside %d" % (inner[0][2], inner[0][3])
-            if "hot_track" in name and (inner[0][3] or scratch):   # (the conditions are the hot builds': some general ones spill SGPRs)
+            if "hot_job_kernel" in name and job_of(name) == "track" and (inner[0][3] or scratch):   # (the conditions are the hot builds': some general ones spill SGPRs)
                 bad += 1
         if name in base:
             # (a label carries the kernel's position in its file, .LBB<position>_<block>: the position is not part of the stream)
